@@ -2,7 +2,7 @@
 """bench.py -- throughput of the MI355X hot path (chaining + gap-fill / split extension) on
 synthetic long reads against a GRCh37-sized stand-in reference.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (lamsa_hp_run_uploaded: kernels + result download) over one
 batch of reads that is already resident in HBM (reference, reads and seed hits uploaded before the
@@ -10,11 +10,15 @@ timed region).  N > 1: launched by torch.distributed.run, one process per GPU, e
 own shard of the read stream (different reads, same reference) -- weak scaling, no collective on
 the data path; only the barrier + MAX-over-ranks of the timing use RCCL.
 
-The JSON line also carries
+A plain run only sets up, warms up, times the K steps and prints the JSON line (headline, ms_per_step,
+per-launch HIP-event times of the timed steps).  --dump-outputs DIR also writes what the last timed step
+returned (see dump_outputs).  --full adds what takes further runs or host work after the timed steps:
   roofline     -- algorithmic HBM bytes per launch (B_read = L + 20 H + 4 Cs + ceil(T/4) + 4 Co + 32 Rn summed
                   over the batch) / kernel time measured with HIP events on the kernel's stream
+  pcie_*       -- the one-call and streamed boundaries (host arrays in, host results out)
   cpu_baseline -- the oracle (plain-C port of the reference's path) on this box's host cores over a bounded
-                  sample of the same batch; a reported baseline, not the target.
+                  sample of the same batch, and the compiled reference where it travelled; a reported baseline,
+                  not the target.
 """
 import argparse
 import json
@@ -55,7 +59,8 @@ def algorithmic_bytes(B, streams, tbases):
 
 
 def count_mapped_bases(B, streams):
-    """Sum of the lengths of reads with at least one mapped record (the 'aligned' of aligned Gbase/s)."""
+    """Sum of the lengths of reads with at least one mapped record (the 'aligned' of aligned Gbase/s).
+    streams: per-read word sequences (lists, or numpy views into the result stream)."""
     tot = 0
     for r, s in enumerate(streams):
         i, ok = 3, False
@@ -133,6 +138,43 @@ def job_rates(dt, totals, steps):
     return totals[0] * steps / dt, totals[1] * steps / dt / 1e9
 
 
+def granted_cpus(ncpu):
+    """CPUs this job may keep busy: the ncpu cores it may run on, capped by a cgroup (v2) CPU quota and by OMP_NUM_THREADS where
+    either is set -- a shared host can show all of its cores and grant a job a share of them."""
+    n = ncpu
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return n
+
+
+DUMP_BYTES = 64_000_000                # --dump-outputs writes at most 64 MB
+
+
+def dump_outputs(d, stream, r_off, r_len, status):
+    """What one step returns to its caller, as float64 .npy files in d (int32 words, exact in float64), at most DUMP_BYTES in all:
+    read_status and read_len (result words per read) of every read, and the result words themselves of a fixed, seeded sample of
+    the reads -- a permutation of the read indices taken in order while the words fit -- concatenated in read order (stream.npy)
+    with the indices of the sampled reads (stream_reads.npy).  Where a read's words lie in the stream the kernels' completion order
+    decides, so the words are regrouped by read."""
+    n = len(r_len)
+    r_len = np.asarray(r_len, np.int64); r_off = np.asarray(r_off, np.int64)
+    budget = max(0, DUMP_BYTES - 3 * 8 * n - 4096) // 8                # words of stream.npy left beside the three per-read arrays and the headers
+    perm = np.random.default_rng(0).permutation(n)
+    k = int(np.searchsorted(np.cumsum(r_len[perm]), budget, side="right"))
+    sel = np.sort(perm[:k])
+    words = np.concatenate([stream[r_off[i]:r_off[i] + r_len[i]] for i in sel]) if k else np.zeros(0, np.int32)
+    os.makedirs(d, exist_ok=True)
+    for name, v in (("read_status", status), ("read_len", r_len), ("stream_reads", sel), ("stream", words)):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,41 +184,29 @@ def main():
     ap.add_argument("--reads", type=int, default=65536, help="reads per batch (= per step) and per GPU; the metric's configuration is 1 M reads over 8 GPUs = 125 k per GPU, "
                     "and one batch holds at most 2^31 seed CIGAR words (~ 125 k reads of this kind)")
     ap.add_argument("--ref-bp", type=int, default=3_100_000_000, help="size of the reference stand-in")
-    ap.add_argument("--threads", type=int, default=0, help="host threads for input generation and the CPU baseline (0 = every core of the box, os.cpu_count())")
+    ap.add_argument("--threads", type=int, default=0, help="host threads for input generation and the CPU baseline (0: the CPUs granted to this job for the "
+                    "generation, see granted_cpus; every core this process may run on for the CPU baseline's probe)")
     ap.add_argument("--stagger-ms", type=float, default=0.0, help="diagnostic: delay between the first two queued steps of a run")
     ap.add_argument("--sequential", action="store_true", help="wait for every step before starting the next (default: consecutive steps are queued two deep)")
-    ap.add_argument("--stream-chunks", type=int, default=16, help="chunks pushed through the streaming boundary for the PCIe-inclusive rate, after the timed region (0: skip; "
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the roofline (with two steps one at a time), the one-call and streamed "
+                    "PCIe-inclusive rates, the CPU baseline and the reference-binary checks; without it the run ends with the timed steps")
+    ap.add_argument("--stream-chunks", type=int, default=16, help="--full: chunks pushed through the streaming boundary for the PCIe-inclusive rate, after the timed region (0: skip; "
                     "profiles use 0 so that every k_align_batch dispatch of the run is a resident-batch step)")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="target duration of the CPU baseline sample (0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="--full: target duration of the CPU baseline sample (0: skip)")
     ap.add_argument("--no-repeats", action="store_true")
-    ap.add_argument("--default-run-reads", type=int, default=768, help="reads of the default-run check after the CPU baseline: `lamsa aln` WITHOUT -R 0 (stage 4, the BWT rescue, on) of the compiled "
+    ap.add_argument("--default-run-reads", type=int, default=768, help="--full: reads of the default-run check after the CPU baseline: `lamsa aln` WITHOUT -R 0 (stage 4, the BWT rescue, on) of the compiled "
                     "reference and of the product binary on a smaller stand-in whose .bwt / .sa `lamsa index --from-pac` builds on the spot (0: skip)")
     ap.add_argument("--default-run-ref-bp", type=int, default=100_000_000, help="size of that stand-in (the FM index of the 3.1 Gbp one takes a quarter of an hour to build)")
-    ap.add_argument("--bare", action="store_true", help="profiling runs: only set-up, warm-up and the timed steps (no one-call / streamed / CPU legs afterwards)")
+    ap.add_argument("--bare", action="store_true", help="--full for profiling runs: the roofline of the timed steps, no further legs (no one-at-a-time / one-call / streamed / CPU legs afterwards)")
     ap.add_argument("--rehearse", action="store_true", help="development only: run the N > 1 code path with the gloo backend and every rank on GPU 0 "
                     "(a one-GPU box cannot run RCCL with two ranks); the driver never passes this")
     a = ap.parse_args()
 
-    import torch
-    import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != a.gpus and world > 1:
         a.gpus = world
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if a.rehearse:
-            local = 0
-            torch.cuda.set_device(0)
-            dist.init_process_group("gloo")
-        else:
-            torch.cuda.set_device(local)
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    device = local if world > 1 else 0
-    red_dev = None if (world == 1 or a.rehearse) else "cuda"
-
     import simbatch
-    import reflib
-    from lamsa_amd import hp
 
     wl = WORKLOADS[a.workload]
     ncpu = os.cpu_count() or 1
@@ -185,14 +215,39 @@ def main():
     except (AttributeError, OSError):
         pass
     threads = ncpu if a.threads <= 0 else max(1, min(a.threads, ncpu))
+    gen_threads = granted_cpus(ncpu) if a.threads <= 0 else threads      # the simulator is CPU-bound, and its output does not depend on its thread count
     if world > 1:
         threads = max(1, threads // world)                 # ranks share the box's cores while they simulate their shards
-    t0 = time.time()
-    ref = simbatch.SimRef(a.ref_bp, n_contigs=24, seed=5, threads=threads, repeats=not a.no_repeats)
-    t_ref = time.time() - t0
-    t0 = time.time()
-    B = simbatch.SimBatch(ref, a.reads, wl["length"], wl["profile"], seed=shard_seed(rank), threads=threads)
-    t_gen = time.time() - t0
+        gen_threads = max(1, gen_threads // world)
+
+    def make_inputs():
+        t0 = time.time()
+        ref = simbatch.SimRef(a.ref_bp, n_contigs=24, seed=5, threads=gen_threads, repeats=not a.no_repeats)
+        t_ref = time.time() - t0
+        t0 = time.time()
+        B = simbatch.SimBatch(ref, a.reads, wl["length"], wl["profile"], seed=shard_seed(rank), threads=gen_threads)
+        return ref, B, t_ref, time.time() - t0
+    # the simulator (C through ctypes, without the GIL) runs while torch loads and the process group forms
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(1) as pool:
+        inputs = pool.submit(make_inputs)
+        import torch
+        import torch.distributed as dist
+        if world > 1:
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            if a.rehearse:
+                local = 0
+                torch.cuda.set_device(0)
+                dist.init_process_group("gloo")
+            else:
+                torch.cuda.set_device(local)
+                dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        ref, B, t_ref, t_gen = inputs.result()
+    device = local if world > 1 else 0
+    red_dev = None if (world == 1 or a.rehearse) else "cuda"
+
+    import reflib
+    from lamsa_amd import hp
 
     P = hp.make_para(wl["read_type"], **wl["over"])
     h = hp.LamsaHp(P, ref=(ref.pac, ref.l_pac, ref.seq_off, ref.seq_len), device=device)
@@ -242,7 +297,11 @@ def main():
     dt = time.perf_counter() - t0
     stream, r_off, r_len, status = raw
     tbases = np.array(h.last_tbases, copy=True); status = np.array(status, copy=True)
-    streams = [stream[int(r_off[i]):int(r_off[i]) + int(r_len[i])].tolist() for i in range(a.reads)]   # untimed: parsing for the report
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, stream, r_off, r_len, status)
+    streams = [stream[int(r_off[i]):int(r_off[i]) + int(r_len[i])] for i in range(a.reads)]    # views into the host buffer the next step reuses
+    if a.full:
+        streams = [s.tolist() for s in streams]         # untimed: parsing for the report (the legs after the timed steps run further steps)
     n_bases = int(B.read_off[-1])
     mapped_bases = count_mapped_bases(B, streams)
     n_fail = int((status != 0).sum())
@@ -250,136 +309,7 @@ def main():
     reads_per_s, gbase_per_s = job_rates(dt, tot, a.steps)
 
     if rank == 0:
-        alg_bytes, parts = algorithmic_bytes(B, streams, tbases)
         lm = dict(zip(LAUNCH_KEYS, [float(x) for x in np.mean(np.array(phase_ms), axis=0)]))
-        work = np.array(h.last_work, dtype=np.int64).reshape(-1, 4) if len(h.last_work) else np.zeros((1, 4), np.int64)
-        cells, pairs, cs_lines = int(work[:, 0].sum()), int(work[:, 1].sum()), int(work[:, 2].sum())
-        k_ms = float(np.mean(kernel_ms))
-        # The hot path is a sequence of launches per step (hp_phase.h); algorithmic bytes by what each launch group touches, every byte once:
-        # chaining reads the hit records (20 B per hit); the fill group (job listing, lane DP, fill) reads the read bases, the 2-bit
-        # reference windows of its DP jobs and the seed CIGARs of the hits that ended up on lines (counted by the kernels, like T),
-        # and writes the records and their CIGARs.  The seed CIGARs of all the other hits are only touched when the batch is made
-        # resident (k_cig8_expand, outside the timed step): `batch_setup` below, not a launch of the step.
-        fill_ms = lm["fill1"] + lm["fill2"]
-        fill_bytes = parts["L"] + int(np.ceil(tbases.astype(np.int64) / 4.0).sum()) + 4 * cs_lines + 4 * parts["Co"] + 32 * parts["Rn"]
-        chain_bytes = 20 * parts["H"]
-        parts["Cs_on_lines"] = cs_lines
-        step_bytes = chain_bytes + fill_bytes
-        groups = [("k_chain1+k_chain2", lm["chain1"] + lm["chain2"], chain_bytes),
-                  ("k_filllist+k_filldp_wave+k_filldp_small+k_fill", fill_ms, fill_bytes)]
-        # the dominant KERNEL of the step: the longest single launch (round-1 dispatches; round 2 is nearly empty on these workloads)
-        per_kernel = lambda m: {"k_chain1": m["chain1"], "k_fill": m["fill1"] - m["dp1_within_fill1"], "k_filldp_wave": m["wave_dp1_within_fill1"],
-                                "k_filldp_small": m["dp1_within_fill1"] - m["list1_within_fill1"] - m["wave_dp1_within_fill1"], "k_filllist": m["list1_within_fill1"]}
-        dom_kernel = max(per_kernel(lm).items(), key=lambda kv: kv[1])[0]
-        pick = lambda m: per_kernel(m)[dom_kernel]
-        dom_ms_timed = pick(lm)
-        # its algorithmic bytes: chaining = the hit records; the wave-per-job DP = the sequences its jobs read and the CIGARs they write (counted
-        # by the kernel); the fill = the fill group's bytes less those
-        wave_bytes = int(lm["wave_jobs_alg_MB"] * 1e6)
-        dom_bytes = {"k_chain1": chain_bytes, "k_filldp_wave": wave_bytes}.get(dom_kernel, max(fill_bytes - wave_bytes, 0))
-        # The launches of the timed region overlap (steps queued two deep): a clean duration of the dominant kernel comes from two
-        # further steps run one at a time, with the same HIP events -- the figure a rocprofv3 --kernel-trace average agrees with.
-        lm_seq = None
-        if not a.sequential and not a.bare:
-            del phase_ms[:]
-            for _ in range(2):
-                h.run_uploaded(fetch=True, raw=True)
-                phase_ms.append([h.last_kernel_ms(i) for i in range(1, N_LAUNCH)])
-            lm_seq = dict(zip(LAUNCH_KEYS, [float(x) for x in np.mean(np.array(phase_ms), axis=0)]))
-        dom_ms = pick(lm_seq) if lm_seq else dom_ms_timed
-        achieved = dom_bytes / max(dom_ms, 1e-6) / 1e6
-        prof = measured_profile(a.workload, a.reads)
-        pk = lambda k, c: (prof.get(k, {}).get("per_dispatch", {}) or {}).get(c)
-        chain_traffic = prof.get("k_chain1", {}).get("hbm_bytes_per_step_upper")
-        valu_fill = sum((pk(k, "SQ_INSTS_VALU") or 0) * (prof.get(k, {}).get("dispatches_per_step") or 1) for k in ("k_fill", "k_filldp_small", "k_filldp_wave", "k_filllist"))
-        roof = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 6),
-                "traffic": prof.get(dom_kernel, {}).get("hbm_bytes_per_step_upper"), "traffic_source": prof.get("_source"),
-                "kernel": dom_kernel, "kernel_ms": round(dom_ms, 3), "kernel_ms_timed_region_overlapped": round(dom_ms_timed, 3),
-                "kernel_ms_rocprof_avg_committed": (prof.get(dom_kernel, {}).get("round1") or {}).get("avg_ms_rocprof") or prof.get(dom_kernel, {}).get("ms_per_step_rocprof"),
-                "issue_busy_committed": {k: {"valu": (v.get("round1") or v).get("valu_busy_frac"), "scalar": (v.get("round1") or v).get("salu_busy_frac")} for k, v in prof.items() if isinstance(v, dict) and (v.get("round1") or v).get("valu_busy_frac") is not None} or None,
-                "algorithmic_bytes_per_launch": int(dom_bytes),
-                "note": "dominant launch of the step; duration = HIP events on the launches' own stream, %s; its algorithmic bytes = the terms of B_read that launch group touches "
-                        "(seed-CIGAR words only of the hits on lines, counted by the kernel)" % ("steps one at a time after the timed region (the timed region queues steps two deep, so its event intervals overlap)" if lm_seq else "timed region"),
-                "whole_step": {"algorithmic_bytes": int(step_bytes), "launch_ms_sum": round(k_ms, 3), "achieved_GBps": round(step_bytes / max(k_ms, 1e-6) / 1e6, 3),
-                               "hbm_traffic_bytes_upper": prof.get("_step_upper"), "hbm_traffic_bytes_lower": prof.get("_step_lower"),
-                               "b_read_formula_bytes": int(alg_bytes)},
-                "batch_setup": {"what": "k_cig8_expand + offset scan when the batch is made resident, outside the timed step", "algorithmic_bytes": int(5 * parts["Cs"])},
-                "launch_groups": [{"launches": g[0], "ms": round(g[1], 3), "algorithmic_bytes": int(g[2]), "achieved_GBps": round(g[2] / max(g[1], 1e-6) / 1e6, 3)} for g in groups],
-                "launch_ms_one_step_at_a_time": {k: round(v, 3) for k, v in lm_seq.items()} if lm_seq else None,
-                "bytes_per_read": round(step_bytes / a.reads, 1), "terms": parts,
-                # the compute side: DP cell updates and chaining edge classifications actually executed
-                "dp_cells_per_step": cells, "gcups": round(cells * a.steps * world / dt / 1e9, 3), "gcups_within_fill_launches": round(cells / max((lm_seq["fill1"] + lm_seq["fill2"]) if lm_seq else fill_ms, 1e-6) / 1e6, 3),      # (launch durations one step at a time when measured)
-                "pair_evals_per_step": pairs, "pair_evals_per_s": round(pairs * a.steps * world / dt, 1), "pair_evals_per_s_within_chain_launches": round(pairs / max((lm_seq or lm)["chain1"] + (lm_seq or lm)["chain2"], 1e-6) * 1e3, 1),
-                # per unit of work, from the committed counter passes of this workload (None without one)
-                "hbm_bytes_per_pair_eval": round(chain_traffic / max(pairs, 1), 2) if chain_traffic else None,
-                "valu_lane_slots_per_cell": round(valu_fill * 64.0 / max(cells, 1), 1) if valu_fill else None,
-                "valu_issue_frac": {k: v.get("valu_issue_frac") for k, v in prof.items() if isinstance(v, dict) and v.get("valu_issue_frac") is not None} or None}
-        # the compute-side ceiling of the DP launch (the path is max-plus DP, not bytes): how busy the two issue ports were (committed counter pass),
-        # what a cell cost in VALU lane-slots, and what the recurrence alone needs (~22 lane operations per cell -- substitution
-        # score 3, M 2, E 4, F 4, H and the direction nibble 6, the matrix store 3 -- before any cross-lane work of a row)
-        wave = prof.get("k_filldp_wave", {})
-        wv_ = wave.get("round1") or wave
-        wave_valu = (wave.get("per_dispatch") or {}).get("SQ_INSTS_VALU") or (wv_.get("per_dispatch") or {}).get("SQ_INSTS_VALU")
-        wave_cells = lm["wave_jobs_Mcells"] * 1e6
-        roof["compute"] = {"kernel": "k_filldp_wave", "valu_busy": wv_.get("valu_busy_frac"), "salu_busy": wv_.get("salu_busy_frac"),
-                           "lane_slots_per_cell": round(wave_valu * 64.0 / wave_cells, 1) if (wave_valu and wave_cells) else None,
-                           "lane_slots_per_cell_recurrence_only": 22, "dp_cells_per_launch": int(wave_cells),
-                           "gcups_of_the_launch": round(wave_cells / max(lm_seq["wave_dp1_within_fill1"] if lm_seq else lm["wave_dp1_within_fill1"], 1e-6) / 1e6, 1) if wave_cells else None,
-                           "source": prof.get("_source")}
-        t_pcie = r_seq = float("nan")
-        if not a.bare:
-            # PCIe-inclusive rate of the one-call boundary (host buffers in, host results out), one untimed step; never `value`
-            t0 = time.perf_counter(); h.upload_batch(Bc); h.run_uploaded(fetch=True, raw=True); t_pcie = time.perf_counter() - t0
-            # the same resident batch one step at a time (every step waited for before the next starts), for comparison with `value`
-            t0 = time.perf_counter()
-            for _ in range(2):
-                h.run_uploaded(fetch=True, raw=True)
-            r_seq = 2 * a.reads / (time.perf_counter() - t0)
-
-        def streamed(Bx, k=4):
-            """k chunks through the streaming boundary (submit/collect, two in flight): upload of chunk i overlaps the kernel of chunk i-1"""
-            t0 = time.perf_counter()
-            h.submit_batch(Bx)
-            for _ in range(1, k):
-                h.submit_batch(Bx); h.collect_batch(raw=True)
-            h.collect_batch(raw=True)
-            return k * a.reads / (time.perf_counter() - t0)
-        r_stream = r_stream_pinned = None
-        if a.stream_chunks > 1 and not a.bare:
-            r_stream = round(streamed(Bc, a.stream_chunks), 2)
-            Bp = hp.pinned_batch(Bc)
-            r_stream_pinned = round(streamed(Bp, a.stream_chunks), 2)
-            Bp.release()
-        cpu = None
-        h.close()                                          # every GPU measurement is taken: the device buffers go back before the product binary (a process of its own) is run beside the reference's
-        if a.cpu_seconds > 0 and world == 1 and not a.bare:               # the CPU baseline is measured on rank 0 of the single-GPU run only
-            lp = reflib.lo_para(wl["read_type"], **wl["over"])
-            probe = min(256, a.reads)                      # estimate the rate on a probe, then size the sample for ~cpu_seconds
-            # The box shows every core of the host but may grant this job a share of them (a CPU quota): the thread count is chosen by
-            # a probe -- all visible cores, 64, 32, 16 -- and the baseline runs with the fastest; `cores` is what it then used.
-            cand = sorted({threads} | {t for t in (64, 32, 16) if t < threads}, reverse=True)
-            rates = {}
-            for t in cand:
-                t0 = time.perf_counter(); reflib.oracle_streams(take_first(B, probe), lp, t); rates[t] = probe / max(time.perf_counter() - t0, 1e-3)
-            cpu_threads = max(rates, key=lambda t: rates[t]); tp = probe / rates[cpu_threads]
-            n_s = int(max(probe, min(a.reads, probe * a.cpu_seconds / max(tp, 1e-3))))
-            sample = take_first(B, n_s)
-            t0 = time.perf_counter(); want = reflib.oracle_streams(sample, lp, cpu_threads); tc = time.perf_counter() - t0
-            same = sum(1 for i in range(n_s) if want[i] == streams[i])
-            cpu = {"value": round(float(sample.read_off[-1]) / tc / 1e9, 6), "unit": "Gbase/s", "cores": cpu_threads, "kind": "port",
-                   "sample": "first %d reads of the rank-0 batch, oracle (plain-C port of the reference path, one read per task) on %d threads (of %d visible cores; "
-                             "probe of %d reads, reads/s by thread count: %s), %.1f s" % (n_s, cpu_threads, threads, probe, ", ".join("%d: %.0f" % (t, rates[t]) for t in cand), tc),
-                   "reads_per_s": round(n_s / tc, 3), "gpu_equals_cpu_on_sample": "%d/%d reads" % (same, n_s), "host_cpu": cpu_model()}
-            try:
-                cpu["reference_binary"] = reference_binary_baseline(B, ref, wl, cpu_threads, a.cpu_seconds)
-            except Exception as e:                           # a reported extra, never a reason to lose the bench line
-                cpu["reference_binary"] = {"error": repr(e)[:200]}
-            if a.default_run_reads > 0 and isinstance(cpu.get("reference_binary"), dict):
-                try:                                         # the reference's DEFAULT run (stage 4 on) against the product's, on an index built here
-                    cpu["reference_binary"]["default_run"] = default_run_check(a.workload, wl, cpu_threads, a.default_run_reads, a.default_run_ref_bp)
-                    cpu["reference_binary"]["gpu_equals_reference_on_sample_default_run"] = cpu["reference_binary"]["default_run"].get("gpu_equals_reference")
-                except Exception as e:
-                    cpu["reference_binary"]["default_run"] = {"error": repr(e)[:300]}
         hits = np.diff(B.hit_off)
         out = {
             "metric": "aligned Gbase/s, %s vs GRCh37-sized stand-in; inputs resident in HBM when the timed region starts (upload excluded: see pcie_inclusive_*)" % wl["desc"], "value": round(gbase_per_s, 6), "unit": "Gbase/s",
@@ -389,14 +319,145 @@ def main():
             "config": {"workload": "%s: %d reads/step/GPU x %d bp; reference stand-in %d bp in 24 contigs, %d repeat copies; seed hits simulated "
                                    "(GEM thresholds, <=200/seed): %.1f hits/seed, %.0f hits/read" % (a.workload, a.reads, wl["length"], ref.l_pac, ref.n_copies, hits.mean() if len(hits) else 0, B.n_hits / max(1, a.reads)),
                        "reads_per_step_per_gpu": a.reads, "read_len": wl["length"], "read_type": wl["read_type"], "parallelism": "reads sharded over %d GPU(s), no collectives" % a.gpus},
-            "reads_not_ok": int(tot[3]), "steps_queued_two_deep": not a.sequential, "reads_per_s_one_step_at_a_time_rank0": None if a.bare else round(r_seq, 2),
-            "pcie_inclusive_reads_per_s": None if a.bare else round(a.reads / t_pcie, 2),
-            "pcie_inclusive_streamed_reads_per_s": {"pageable_host_arrays": r_stream, "pinned_host_arrays": r_stream_pinned, "chunks": a.stream_chunks},
+            "reads_not_ok": int(tot[3]), "steps_queued_two_deep": not a.sequential,
             "setup_s": {"reference": round(t_ref, 1), "reads_and_hits": round(t_gen, 1)},
             "launch_ms": {k: round(v, 3) for k, v in lm.items()},
-            "roofline": roof, "cpu_baseline": cpu,
-            "library": dict(zip(("path", "sha256"), hp.loaded_library())),
         }
+        if a.full:
+            alg_bytes, parts = algorithmic_bytes(B, streams, tbases)
+            work = np.array(h.last_work, dtype=np.int64).reshape(-1, 4) if len(h.last_work) else np.zeros((1, 4), np.int64)
+            cells, pairs, cs_lines = int(work[:, 0].sum()), int(work[:, 1].sum()), int(work[:, 2].sum())
+            k_ms = float(np.mean(kernel_ms))
+            # The hot path is a sequence of launches per step (hp_phase.h); algorithmic bytes by what each launch group touches, every byte once:
+            # chaining reads the hit records (20 B per hit); the fill group (job listing, lane DP, fill) reads the read bases, the 2-bit
+            # reference windows of its DP jobs and the seed CIGARs of the hits that ended up on lines (counted by the kernels, like T),
+            # and writes the records and their CIGARs.  The seed CIGARs of all the other hits are only touched when the batch is made
+            # resident (k_cig8_expand, outside the timed step): `batch_setup` below, not a launch of the step.
+            fill_ms = lm["fill1"] + lm["fill2"]
+            fill_bytes = parts["L"] + int(np.ceil(tbases.astype(np.int64) / 4.0).sum()) + 4 * cs_lines + 4 * parts["Co"] + 32 * parts["Rn"]
+            chain_bytes = 20 * parts["H"]
+            parts["Cs_on_lines"] = cs_lines
+            step_bytes = chain_bytes + fill_bytes
+            groups = [("k_chain1+k_chain2", lm["chain1"] + lm["chain2"], chain_bytes),
+                      ("k_filllist+k_filldp_wave+k_filldp_small+k_fill", fill_ms, fill_bytes)]
+            # the dominant KERNEL of the step: the longest single launch (round-1 dispatches; round 2 is nearly empty on these workloads)
+            per_kernel = lambda m: {"k_chain1": m["chain1"], "k_fill": m["fill1"] - m["dp1_within_fill1"], "k_filldp_wave": m["wave_dp1_within_fill1"],
+                                    "k_filldp_small": m["dp1_within_fill1"] - m["list1_within_fill1"] - m["wave_dp1_within_fill1"], "k_filllist": m["list1_within_fill1"]}
+            dom_kernel = max(per_kernel(lm).items(), key=lambda kv: kv[1])[0]
+            pick = lambda m: per_kernel(m)[dom_kernel]
+            dom_ms_timed = pick(lm)
+            # its algorithmic bytes: chaining = the hit records; the wave-per-job DP = the sequences its jobs read and the CIGARs they write (counted
+            # by the kernel); the fill = the fill group's bytes less those
+            wave_bytes = int(lm["wave_jobs_alg_MB"] * 1e6)
+            dom_bytes = {"k_chain1": chain_bytes, "k_filldp_wave": wave_bytes}.get(dom_kernel, max(fill_bytes - wave_bytes, 0))
+            # The launches of the timed region overlap (steps queued two deep): a clean duration of the dominant kernel comes from two
+            # further steps run one at a time, with the same HIP events -- the figure a rocprofv3 --kernel-trace average agrees with.
+            lm_seq = None
+            if not a.sequential and not a.bare:
+                del phase_ms[:]
+                for _ in range(2):
+                    h.run_uploaded(fetch=True, raw=True)
+                    phase_ms.append([h.last_kernel_ms(i) for i in range(1, N_LAUNCH)])
+                lm_seq = dict(zip(LAUNCH_KEYS, [float(x) for x in np.mean(np.array(phase_ms), axis=0)]))
+            dom_ms = pick(lm_seq) if lm_seq else dom_ms_timed
+            achieved = dom_bytes / max(dom_ms, 1e-6) / 1e6
+            prof = measured_profile(a.workload, a.reads)
+            pk = lambda k, c: (prof.get(k, {}).get("per_dispatch", {}) or {}).get(c)
+            chain_traffic = prof.get("k_chain1", {}).get("hbm_bytes_per_step_upper")
+            valu_fill = sum((pk(k, "SQ_INSTS_VALU") or 0) * (prof.get(k, {}).get("dispatches_per_step") or 1) for k in ("k_fill", "k_filldp_small", "k_filldp_wave", "k_filllist"))
+            roof = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 6),
+                    "traffic": prof.get(dom_kernel, {}).get("hbm_bytes_per_step_upper"), "traffic_source": prof.get("_source"),
+                    "kernel": dom_kernel, "kernel_ms": round(dom_ms, 3), "kernel_ms_timed_region_overlapped": round(dom_ms_timed, 3),
+                    "kernel_ms_rocprof_avg_committed": (prof.get(dom_kernel, {}).get("round1") or {}).get("avg_ms_rocprof") or prof.get(dom_kernel, {}).get("ms_per_step_rocprof"),
+                    "issue_busy_committed": {k: {"valu": (v.get("round1") or v).get("valu_busy_frac"), "scalar": (v.get("round1") or v).get("salu_busy_frac")} for k, v in prof.items() if isinstance(v, dict) and (v.get("round1") or v).get("valu_busy_frac") is not None} or None,
+                    "algorithmic_bytes_per_launch": int(dom_bytes),
+                    "note": "dominant launch of the step; duration = HIP events on the launches' own stream, %s; its algorithmic bytes = the terms of B_read that launch group touches "
+                            "(seed-CIGAR words only of the hits on lines, counted by the kernel)" % ("steps one at a time after the timed region (the timed region queues steps two deep, so its event intervals overlap)" if lm_seq else "timed region"),
+                    "whole_step": {"algorithmic_bytes": int(step_bytes), "launch_ms_sum": round(k_ms, 3), "achieved_GBps": round(step_bytes / max(k_ms, 1e-6) / 1e6, 3),
+                                   "hbm_traffic_bytes_upper": prof.get("_step_upper"), "hbm_traffic_bytes_lower": prof.get("_step_lower"),
+                                   "b_read_formula_bytes": int(alg_bytes)},
+                    "batch_setup": {"what": "k_cig8_expand + offset scan when the batch is made resident, outside the timed step", "algorithmic_bytes": int(5 * parts["Cs"])},
+                    "launch_groups": [{"launches": g[0], "ms": round(g[1], 3), "algorithmic_bytes": int(g[2]), "achieved_GBps": round(g[2] / max(g[1], 1e-6) / 1e6, 3)} for g in groups],
+                    "launch_ms_one_step_at_a_time": {k: round(v, 3) for k, v in lm_seq.items()} if lm_seq else None,
+                    "bytes_per_read": round(step_bytes / a.reads, 1), "terms": parts,
+                    # the compute side: DP cell updates and chaining edge classifications actually executed
+                    "dp_cells_per_step": cells, "gcups": round(cells * a.steps * world / dt / 1e9, 3), "gcups_within_fill_launches": round(cells / max((lm_seq["fill1"] + lm_seq["fill2"]) if lm_seq else fill_ms, 1e-6) / 1e6, 3),      # (launch durations one step at a time when measured)
+                    "pair_evals_per_step": pairs, "pair_evals_per_s": round(pairs * a.steps * world / dt, 1), "pair_evals_per_s_within_chain_launches": round(pairs / max((lm_seq or lm)["chain1"] + (lm_seq or lm)["chain2"], 1e-6) * 1e3, 1),
+                    # per unit of work, from the committed counter passes of this workload (None without one)
+                    "hbm_bytes_per_pair_eval": round(chain_traffic / max(pairs, 1), 2) if chain_traffic else None,
+                    "valu_lane_slots_per_cell": round(valu_fill * 64.0 / max(cells, 1), 1) if valu_fill else None,
+                    "valu_issue_frac": {k: v.get("valu_issue_frac") for k, v in prof.items() if isinstance(v, dict) and v.get("valu_issue_frac") is not None} or None}
+            # the compute-side ceiling of the DP launch (the path is max-plus DP, not bytes): how busy the two issue ports were (committed counter pass),
+            # what a cell cost in VALU lane-slots, and what the recurrence alone needs (~22 lane operations per cell -- substitution
+            # score 3, M 2, E 4, F 4, H and the direction nibble 6, the matrix store 3 -- before any cross-lane work of a row)
+            wave = prof.get("k_filldp_wave", {})
+            wv_ = wave.get("round1") or wave
+            wave_valu = (wave.get("per_dispatch") or {}).get("SQ_INSTS_VALU") or (wv_.get("per_dispatch") or {}).get("SQ_INSTS_VALU")
+            wave_cells = lm["wave_jobs_Mcells"] * 1e6
+            roof["compute"] = {"kernel": "k_filldp_wave", "valu_busy": wv_.get("valu_busy_frac"), "salu_busy": wv_.get("salu_busy_frac"),
+                               "lane_slots_per_cell": round(wave_valu * 64.0 / wave_cells, 1) if (wave_valu and wave_cells) else None,
+                               "lane_slots_per_cell_recurrence_only": 22, "dp_cells_per_launch": int(wave_cells),
+                               "gcups_of_the_launch": round(wave_cells / max(lm_seq["wave_dp1_within_fill1"] if lm_seq else lm["wave_dp1_within_fill1"], 1e-6) / 1e6, 1) if wave_cells else None,
+                               "source": prof.get("_source")}
+            t_pcie = r_seq = float("nan")
+            if not a.bare:
+                # PCIe-inclusive rate of the one-call boundary (host buffers in, host results out), one untimed step; never `value`
+                t0 = time.perf_counter(); h.upload_batch(Bc); h.run_uploaded(fetch=True, raw=True); t_pcie = time.perf_counter() - t0
+                # the same resident batch one step at a time (every step waited for before the next starts), for comparison with `value`
+                t0 = time.perf_counter()
+                for _ in range(2):
+                    h.run_uploaded(fetch=True, raw=True)
+                r_seq = 2 * a.reads / (time.perf_counter() - t0)
+
+            def streamed(Bx, k=4):
+                """k chunks through the streaming boundary (submit/collect, two in flight): upload of chunk i overlaps the kernel of chunk i-1"""
+                t0 = time.perf_counter()
+                h.submit_batch(Bx)
+                for _ in range(1, k):
+                    h.submit_batch(Bx); h.collect_batch(raw=True)
+                h.collect_batch(raw=True)
+                return k * a.reads / (time.perf_counter() - t0)
+            r_stream = r_stream_pinned = None
+            if a.stream_chunks > 1 and not a.bare:
+                r_stream = round(streamed(Bc, a.stream_chunks), 2)
+                Bp = hp.pinned_batch(Bc)
+                r_stream_pinned = round(streamed(Bp, a.stream_chunks), 2)
+                Bp.release()
+            cpu = None
+            h.close()                                          # every GPU measurement is taken: the device buffers go back before the product binary (a process of its own) is run beside the reference's
+            if a.cpu_seconds > 0 and world == 1 and not a.bare:               # the CPU baseline is measured on rank 0 of the single-GPU run only
+                lp = reflib.lo_para(wl["read_type"], **wl["over"])
+                probe = min(256, a.reads)                      # estimate the rate on a probe, then size the sample for ~cpu_seconds
+                # The box shows every core of the host but may grant this job a share of them (a CPU quota): the thread count is chosen by
+                # a probe -- all visible cores, 64, 32, 16 -- and the baseline runs with the fastest; `cores` is what it then used.
+                cand = sorted({threads} | {t for t in (64, 32, 16) if t < threads}, reverse=True)
+                rates = {}
+                for t in cand:
+                    t0 = time.perf_counter(); reflib.oracle_streams(take_first(B, probe), lp, t); rates[t] = probe / max(time.perf_counter() - t0, 1e-3)
+                cpu_threads = max(rates, key=lambda t: rates[t]); tp = probe / rates[cpu_threads]
+                n_s = int(max(probe, min(a.reads, probe * a.cpu_seconds / max(tp, 1e-3))))
+                sample = take_first(B, n_s)
+                t0 = time.perf_counter(); want = reflib.oracle_streams(sample, lp, cpu_threads); tc = time.perf_counter() - t0
+                same = sum(1 for i in range(n_s) if want[i] == streams[i])
+                cpu = {"value": round(float(sample.read_off[-1]) / tc / 1e9, 6), "unit": "Gbase/s", "cores": cpu_threads, "kind": "port",
+                       "sample": "first %d reads of the rank-0 batch, oracle (plain-C port of the reference path, one read per task) on %d threads (of %d visible cores; "
+                                 "probe of %d reads, reads/s by thread count: %s), %.1f s" % (n_s, cpu_threads, threads, probe, ", ".join("%d: %.0f" % (t, rates[t]) for t in cand), tc),
+                       "reads_per_s": round(n_s / tc, 3), "gpu_equals_cpu_on_sample": "%d/%d reads" % (same, n_s), "host_cpu": cpu_model()}
+                try:
+                    cpu["reference_binary"] = reference_binary_baseline(B, ref, wl, cpu_threads, a.cpu_seconds)
+                except Exception as e:                           # a reported extra, never a reason to lose the bench line
+                    cpu["reference_binary"] = {"error": repr(e)[:200]}
+                if a.default_run_reads > 0 and isinstance(cpu.get("reference_binary"), dict):
+                    try:                                         # the reference's DEFAULT run (stage 4 on) against the product's, on an index built here
+                        cpu["reference_binary"]["default_run"] = default_run_check(a.workload, wl, cpu_threads, a.default_run_reads, a.default_run_ref_bp)
+                        cpu["reference_binary"]["gpu_equals_reference_on_sample_default_run"] = cpu["reference_binary"]["default_run"].get("gpu_equals_reference")
+                    except Exception as e:
+                        cpu["reference_binary"]["default_run"] = {"error": repr(e)[:300]}
+            out.update({"reads_per_s_one_step_at_a_time_rank0": None if a.bare else round(r_seq, 2),
+                        "pcie_inclusive_reads_per_s": None if a.bare else round(a.reads / t_pcie, 2),
+                        "pcie_inclusive_streamed_reads_per_s": {"pageable_host_arrays": r_stream, "pinned_host_arrays": r_stream_pinned, "chunks": a.stream_chunks},
+                        "roofline": roof, "cpu_baseline": cpu})
+        out["library"] = dict(zip(("path", "sha256"), hp.loaded_library()))
         print(json.dumps(out))
     h.close()
     if world > 1:

@@ -13,7 +13,7 @@ import pytest
 import reflib
 
 ROOT = reflib.ROOT
-NEED = [os.path.join(ROOT, "oracle", "_ref", "lamsa"), "/root/reference/gem"]
+NEED = [os.path.join(ROOT, "oracle", "_ref", "lamsa"), os.path.join(ROOT, "oracle", "_ref", "gem", "gem-mapper")]      # the GEM bundle: linked there by `make -C oracle ref`
 
 
 @pytest.mark.skipif(not all(os.path.exists(p) for p in NEED), reason="needs the compiled reference and its GEM bundle")

@@ -1,10 +1,10 @@
 #!/bin/bash
-# One full check on the GPU box (through gpurun): every -m gpu test, then the default bench line as the driver runs it.   tools/full_gpu.sh <tag>
+# One full check on the GPU box: every -m gpu test, then the default bench line with every leg (--full).   tools/full_gpu.sh <tag>
 tag=${1:-full}
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-timeout -k 10 800 python3 -m pytest tests -m gpu -x -q > gpurun_out/${tag}_pytest.log 2>&1; tail -3 gpurun_out/${tag}_pytest.log
-( time timeout -k 10 600 python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err ) 2>&1 | grep real
-python3 - gpurun_out/${tag}_bench.json <<'PY'
+cd "$(dirname "$0")/.."; out=${BENCH_OUT:-bench_out}; mkdir -p $out
+timeout -k 10 800 python3 -m pytest tests -m gpu -x -q > $out/${tag}_pytest.log 2>&1; tail -3 $out/${tag}_pytest.log
+( time timeout -k 10 600 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err ) 2>&1 | grep real
+python3 - $out/${tag}_bench.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print("value", d["value"], "reads/s", d["reads_per_s"], "ms/step", d["ms_per_step"], "bad", d["reads_not_ok"])

@@ -9,7 +9,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 # one launch at a time (--sequential): the timed region of a plain run queues steps two deep, and the trace would show every kernel stretched by the one it shares the GPU with
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py "$@" --sequential --bare > $out/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py "$@" --sequential --bare --full > $out/bench_stats.log 2>&1
 # PMC_SETS="FETCH_SIZE;WRITE_SIZE" limits the counter passes (default: all five)
 if [ -n "${PMC_SETS:-}" ]; then IFS=';' read -ra SETS <<< "$PMC_SETS"; else
 SETS=("SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS"
