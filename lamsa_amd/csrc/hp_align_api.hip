@@ -50,13 +50,15 @@ template <int WORDS, int WPS>
 __global__ __launch_bounds__(64, WPS) void k_chain1(const PhaseArgs *ap)
 {
     const PhaseArgs &a = *ap;        // in device memory: scalar loads, no private copy of the argument block
-    __shared__ int32_t lds[WORDS];   // the hit sort's blocks (hp_sort.h), then the node state of one cluster at a time (hp_cluster.h)
+    constexpr bool ctx_lds = ph_ctx_in_lds(WORDS, WPS);
+    __shared__ alignas(16) int32_t lds[WORDS + (ctx_lds ? PH_CTX_BYTES / 4 : 0)];   // the hit sort's blocks (hp_sort.h), then the node state of one cluster at a time (hp_cluster.h); the read context
+    ReadCtx &r = *(ctx_lds ? (ReadCtx *)(lds + WORDS) : (ReadCtx *)(a.slab + (size_t)blockIdx.x * a.slab_per_wave));
     for (;;) {
         int u = 0;
         if (wv::leader()) u = atomicAdd(&a.ctl->q_head[0], 1);
         u = wv::uni(u);
         if (u >= a.n_reads) break;
-        phase_chain1(a, a.order ? a.order[u] : u, blockIdx.x, (HP_L int32_t *)lds, WORDS);
+        phase_chain1(a, a.order ? a.order[u] : u, blockIdx.x, (HP_L int32_t *)lds, WORDS, r);
     }
     drain_stamp(a, 0);
 }
@@ -64,13 +66,15 @@ template <int WORDS, int WPS>
 __global__ __launch_bounds__(64, WPS) void k_chain2(const PhaseArgs *ap)
 {
     const PhaseArgs &a = *ap;
-    __shared__ int32_t lds[WORDS];
+    constexpr bool ctx_lds = ph_ctx_in_lds(WORDS, WPS);
+    __shared__ alignas(16) int32_t lds[WORDS + (ctx_lds ? PH_CTX_BYTES / 4 : 0)];
+    ReadCtx &r = *(ctx_lds ? (ReadCtx *)(lds + WORDS) : (ReadCtx *)(a.slab + (size_t)blockIdx.x * a.slab_per_wave));
     for (;;) {
         int u = 0;
         if (wv::leader()) u = atomicAdd(&a.ctl->q_head[2], 1);
         u = wv::uni(u);
         if (u >= a.n_reads) break;
-        phase_chain2(a, a.order ? a.order[u] : u, blockIdx.x, (HP_L int32_t *)lds, WORDS);
+        phase_chain2(a, a.order ? a.order[u] : u, blockIdx.x, (HP_L int32_t *)lds, WORDS, r);
     }
     drain_stamp(a, 2);
 }

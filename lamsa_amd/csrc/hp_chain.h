@@ -1731,9 +1731,13 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
     { const long long t2_ = wv::clock(); if (r.prof) r.prof[57] += t2_ - tq_; tq_ = t2_; }
 #endif
     if (all_min) min_n = P->per_aln_m;
+    // the records that the routines below fill or update, once per wave in the arena (a local of this frame would be a copy per lane)
+    struct Loc { Clusters C; NScore ns; LSet L, S; Trig T; };
+    Loc *loc = (Loc *)arena_alloc(r.cx, sizeof(Loc));
+    if (!loc) return false;
     // the clusters of the read's hits (hp_cluster.h): what frag_min_extend and the main pass below work on
     const size_t cmark = arena_mark(r.cx.tmp);
-    Clusters C;
+    Clusters &C = loc->C;
     bool have_cl = false;
     if (seed_out > 1 && HP_CL_CAP_RT(1) > 0) {
         have_cl = clusters_build(r, C, (HP_L uint64_t *)r.cx.lds, r.cx.lds_words / 2);
@@ -1790,7 +1794,7 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
 #if defined(HP_CHAIN_STOP) && HP_CHAIN_STOP == 2
     return true;
 #endif
-    NScore ns;
+    NScore &ns = loc->ns;
     if (!ns_alloc(r.cx, ns, H + 1, 0)) return false;
     ns.min_score_thd = 2;
     track_leaves(r, 0, seed_out - 1, MIN_FLAG, ns);                                                 // :1356-1361
@@ -1800,8 +1804,8 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
     return true;
 #endif
     const int o_l = ns.node_n;
-    LSet L;
-    Trig T;
+    LSet &L = loc->L;
+    Trig &T = loc->T;
     if (!lset_alloc(r.cx, L, 2 * H + o_l + 16, o_l)) return false;
     T.cap = 2 * H + 2 * o_l + 16; T.used = 0;
     T.n1 = (int32_t *)arena_alloc(r.cx, sizeof(int32_t) * (size_t)T.cap);
@@ -1817,7 +1821,7 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
 #if defined(HP_CHAIN_STOP) && HP_CHAIN_STOP == 4
     return true;
 #endif
-    LSet S;
+    LSet &S = loc->S;
     const bool staged = lset_stage(r, L, l_i, S);                     // the per-line arrays in LDS from here on, when they fit
     LSet &LL = staged ? S : L;
     const int line_n = set_bound(r, LL, 0, l_i, &T);                  // :1435
@@ -1845,7 +1849,9 @@ HP_NOINL int multi_line(ReadCtx &r, int left_b, int right_b, const Regs &G, int 
     nodes_per_init(r, hoff(r, start), hoff(r, end + 1), -1, dp_flag, 1);
     if (start + 1 <= end) dp_update_range(r, hoff(r, start + 1), hoff(r, end + 1), start, dp_flag, false, true);
     const size_t mark = arena_mark(r.cx.tmp);
-    NScore ns;
+    NScore *nsp = (NScore *)arena_alloc(r.cx, sizeof(NScore));       // once per wave, not in every lane's frame
+    if (!nsp) return 0;
+    NScore &ns = *nsp;
     if (!ns_alloc(r.cx, ns, hoff(r, end + 1) - hoff(r, start) + 1, 0)) return 0;
     ns.min_score_thd = 0;
     track_leaves(r, start, end, dp_flag, ns);
@@ -1890,7 +1896,9 @@ HP_NOINL bool chain_remain(ReadCtx &r, const Regs &G, FLines &F, FlStore *fs = n
     const lamsa_hp_para *P = r.cx.P;
     const int seed_out = r.seed_out, H = r.H;
     F.n = 0; F.nfrag = 0;
-    LSet L, T;
+    LSet *lt = (LSet *)arena_alloc(r.cx, 2 * sizeof(LSet));             // once per wave, not in every lane's frame
+    if (!lt) return false;
+    LSet &L = lt[0], &T = lt[1];
     if (!lset_alloc(r.cx, L, H + 16, H + 1) || !lset_alloc(r.cx, T, H + 16, H + 1)) return false;
     int l_n = 0, next_start = 0;
     for (int i = 0; i < G.m; ++i) {

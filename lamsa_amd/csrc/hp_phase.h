@@ -158,21 +158,35 @@ HP_INL void pers_bind(ReadCtx &r, const PhaseArgs &a, int rd)
 #define PH_TMID(k, v) do { } while (0)
 #endif
 
-HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words = HP_CHAIN_LDS_WORDS)
+// The read context of the chaining kernels is held once per wave, not once per lane: `r` is the wave's block of PH_CTX_BYTES in LDS next
+// to the chaining words where the CU has room for it (the 4-wave shape, ph_ctx_in_lds), else the head of the wave's slab, which the
+// arena then starts behind.  As a local of the phase it lived in every lane's scratch -- 64 copies of the same 432 bytes, every field
+// read of a callee a per-lane load from HBM.  The records that the chaining routines fill for their callers
+// (FLines, FlStore, Clusters, LSet, Trig, NScore, Regs) are allocated from the wave's arena for the same reason.
+// A slab is never below 64 KiB (lamsa_hp_set_scratch_limit), so the block always fits.
+enum { PH_CTX_BYTES = 512 };
+static_assert(sizeof(ReadCtx) <= PH_CTX_BYTES, "the read context must fit its per-wave block");
+constexpr bool ph_ctx_in_lds(int words, int waves_per_simd)
+{
+    return 4 * waves_per_simd * (((size_t)words * 4 + PH_CTX_BYTES + 511) / 512 * 512) <= 160 * 1024;
+}
+struct ChainOut { FLines F; FlStore fs; };     // what chain_first / chain_remain leave for units_push
+
+HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words, ReadCtx &r)
 {
 #ifdef HP_PROF
     long long ph_t_ = wv::clock();
 #endif
     if (a.in.read_skip && a.in.read_skip[rd]) { if (wv::leader()) atomicOr(&a.meta[rd].status, ST_UNSUPPORTED); return; }       // refused by the batch check: no result
-    ReadCtx r;
-    read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_per_wave, a.slab_per_wave, lds, a.prof, lds_words);
+    read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_per_wave + PH_CTX_BYTES, a.slab_per_wave - PH_CTX_BYTES, lds, a.prof, lds_words);
     pers_bind(r, a, rd);
     Ctx &cx = r.cx;
     const int H = r.H, c = H + 1;
+    ChainOut *co = (ChainOut *)arena_alloc(cx, sizeof(ChainOut));
     int32_t *nm = (int32_t *)arena_alloc(cx, sizeof(int32_t) * 10 * (size_t)c);
     const size_t sort_mark = arena_mark(cx.tmp);
     uint64_t *sort_work = (uint64_t *)arena_alloc(cx, sizeof(uint64_t) * (size_t)c);
-    if (nm && sort_work) {
+    if (co && nm && sort_work) {
         int32_t *sidx = a.g_sidx + 2 * (r.hb + rd);
         { HP_T0(t_sort_);
         sort_read_hits(r.h_pos, r.h_chr, r.h_strand, H, sidx, sidx + c, sort_work, (HP_L uint64_t *)lds, lds_words / 2, a.sort_pb, a.sort_cb);
@@ -181,8 +195,8 @@ HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
         aux_bind(r, nm);
         nodes_fill(r);
         PH_TMID(0, ph_t_);
-        FLines F;
-        FlStore fs; fs.base = a.fl_base; fs.cap = a.fl_cap; fs.cursor = &a.ctl->fl_cursor; fs.got_off = 0; fs.got_tot = 0;
+        FLines &F = co->F;
+        FlStore &fs = co->fs; fs.base = a.fl_base; fs.cap = a.fl_cap; fs.cursor = &a.ctl->fl_cursor; fs.got_off = 0; fs.got_tot = 0;
 #if defined(HP_CHAIN_STOP) && HP_CHAIN_STOP == 0
         const bool ok1 = true; F.n = 0; F.nfrag = 0;       // traffic experiment (tools/chain_stops.sh): sort index and node records only
 #else
@@ -193,6 +207,13 @@ HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
         else if (!ok1 && !(cx.status & (ST_REFEXIT | ST_OVERFLOW))) cx.status |= ST_OVERFLOW;
     }
     meta_flag(a, rd, r);
+}
+
+// the same with a read context of the calling frame (the one-wave-at-a-time CPU emulation of the tests)
+HP_FN void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words = HP_CHAIN_LDS_WORDS)
+{
+    ReadCtx r;
+    phase_chain1(a, rd, wave_slot, lds, lds_words, r);
 }
 
 // ---------------------------------------------------------------- fill: one line of one read
@@ -646,19 +667,21 @@ void phase_wavejob(const PhaseArgs &a, int round, int g, bool big, int wave_slot
 }
 
 // ---------------------------------------------------------------- chain2: one read
-HP_NOINL void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words = HP_CHAIN_LDS_WORDS)
+HP_NOINL void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words, ReadCtx &r)
 {
     RdMeta &M = a.meta[rd];
     if (M.status & ST_DEAD) return;
     PH_T0();
-    ReadCtx r;
-    read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_per_wave, a.slab_per_wave, lds, a.prof, lds_words);
+    read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_per_wave + PH_CTX_BYTES, a.slab_per_wave - PH_CTX_BYTES, lds, a.prof, lds_words);
     pers_bind(r, a, rd);
     Ctx &cx = r.cx;
     const int H = r.H, c = H + 1;
+    ChainOut *co = (ChainOut *)arena_alloc(cx, sizeof(ChainOut));
+    Regs *gp = (Regs *)arena_alloc(cx, sizeof(Regs));
+    if (!co || !gp) { meta_flag(a, rd, r); return; }
     int32_t *nm = (int32_t *)arena_alloc(cx, sizeof(int32_t) * 10 * (size_t)c);
     const int reg_cap = 256;
-    Regs G; G.n = 0; G.m = 0;
+    Regs &G = *gp; G.n = 0; G.m = 0;
     G.beg = (int32_t *)arena_alloc(cx, sizeof(int32_t) * 2 * (size_t)reg_cap); G.end = G.beg + reg_cap;
     G.rb = (RegB *)arena_alloc(cx, sizeof(RegB) * 2 * (size_t)reg_cap); G.re = G.rb + reg_cap;
     G.r_beg = (int32_t *)arena_alloc(cx, sizeof(int32_t) * 6 * (size_t)(reg_cap + 2));
@@ -680,8 +703,8 @@ HP_NOINL void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
         wv::sync();
         if (!(cx.status & ST_OVERFLOW)) {
             regs_remain(r, G, a.P.seed_len, r.L);
-            FLines F;
-            FlStore fs; fs.base = a.fl_base; fs.cap = a.fl_cap; fs.cursor = &a.ctl->fl_cursor; fs.got_off = 0; fs.got_tot = 0;
+            FLines &F = co->F;
+            FlStore &fs = co->fs; fs.base = a.fl_base; fs.cap = a.fl_cap; fs.cursor = &a.ctl->fl_cursor; fs.got_off = 0; fs.got_tot = 0;
             const bool ok2 = chain_remain(r, G, F, &fs);
             if (ok2 && F.n > 0) units_push(a, r, rd, 1, F, fs);
             else if (!ok2 && !(cx.status & (ST_REFEXIT | ST_OVERFLOW))) cx.status |= ST_OVERFLOW;
@@ -689,6 +712,12 @@ HP_NOINL void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
     }
     PH_TADD(3);
     meta_flag(a, rd, r);
+}
+
+HP_FN void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words = HP_CHAIN_LDS_WORDS)
+{
+    ReadCtx r;
+    phase_chain2(a, rd, wave_slot, lds, lds_words, r);
 }
 
 // ---------------------------------------------------------------- publish: one read's result stream
