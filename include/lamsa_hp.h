@@ -151,8 +151,12 @@ typedef struct lamsa_hp_batch {
  *   [0] status bits (LAMSA_HP_ST_*)  [1] lines of round 1 (a_res[0].l_n)  [2] lines of round 2 (a_res[1].l_n)
  *   per line : line_score, tol_score, tol_NM, n_res (= cur_res_n+1, 0 when every record was dropped)
  *   per res  : offset_lo, offset_hi, chr, nstrand (1 '+', 0 '-'), score (AS), NM, cigar_n, cigar words...
+ *              and, only with LAMSA_HP_TAG_MISMATCHES set (lamsa_hp_set_result_tags), after the CIGAR words:
+ *              n_mm, then n_mm words ref_off << 2 | base, ref_off ascending
  * i.e. the fields of line_aln_res / res_t (src/frag_check.h:46-73) that aln_res_output and
- * rearr_aln_res consume. */
+ * rearr_aln_res consume.  A mismatch word names one aligned base that differs from the reference: ref_off is its
+ * 0-based offset from the record's offset (POS) on the forward reference, base the .pac code (0-3) of the reference
+ * base there.  A read N (code 4) is a mismatch, as it is for NM; so NM = n_mm + inserted + deleted bases. */
 typedef struct lamsa_hp_result {
     const int32_t *stream; int64_t stream_words;
     const int64_t *read_off;      /* [n_reads] start of read r's stream */
@@ -164,6 +168,12 @@ typedef struct lamsa_hp_result {
 } lamsa_hp_result;
 
 int lamsa_hp_align_batch(lamsa_hp_handle *h, const lamsa_hp_batch *batch, lamsa_hp_result *res);
+
+/* Optional items of the result stream (lamsa_hp_result), for the batches aligned after the call; 0 (the default) is the
+ * stream as documented without them.  LAMSA_HP_TAG_MISMATCHES: every record also lists its mismatches (what a SAM
+ * writer needs for MD:Z without reading the reference again).  LAMSA_HP_EINVAL while a batch or run is in flight. */
+#define LAMSA_HP_TAG_MISMATCHES 1
+int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags);
 
 /* The same in two steps, so that a caller can keep a batch resident in HBM and overlap or
  * repeat the compute: upload copies the batch to the device, run aligns the resident batch

@@ -84,11 +84,31 @@ HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
             wv::sync();
         }
         else cx.status |= ST_OVERFLOW;
+        if (la.ev) {                                                  // LAMSA_HP_TAG_MISMATCHES: the record's mismatch list (res_aux)
+            const int nm = rec.n_mm;
+            out_put(cx, o, nm);
+            if (o.n + nm <= o.cap) {
+                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
+                const HP_G int32_t *src = (const HP_G int32_t *)rec.mm;
+                wv::sync();
+                for (int b0 = 0; b0 < nm; b0 += 64) { WAVE_FOR(l) { const int k = b0 + l; if (k < nm) dst[k] = src[k]; } }
+                o.n += nm;
+                wv::sync();
+            }
+            else cx.status |= ST_OVERFLOW;
+        }
     }
 }
 
+// LAMSA_HP_TAG_MISMATCHES: the mismatch lists of a line (LineRes::ev) -- at most one per aligned read base, the records of a line
+// cover disjoint parts of the read -- and what they add to the line's result words (the lists and a count per record)
+HP_INL int line_ev_cap(int L) { return L + 64; }
+HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
+// words of a read's result stream on the one-kernel path (align_read); the second pass sizes its arena by it
+HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + (tags ? 4LL * L + 4 * HP_REC_MAX : 0)) * scale; }
+
 // frag_check over all lines of one round (frag_check.c:886-955) + get_reg (lamsa_aln.c:597) for round 1
-HP_NOINL void fill_round(ReadCtx &r, FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale)
+HP_NOINL void fill_round(ReadCtx &r, FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
 {
     Ctx &cx = r.cx;
     const size_t mark = arena_mark(cx.tmp);
@@ -96,7 +116,10 @@ HP_NOINL void fill_round(ReadCtx &r, FLines &F, OutBuf &o, Regs *G, int reg_cap,
     LineRes *la = (LineRes *)arena_alloc(cx, sizeof(LineRes));
     cig_t *cur_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)cur_cap);
     cig_t *rec_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)(cur_cap + 4 * HP_REC_MAX));
-    if (!la || !cur_buf || !rec_buf) { arena_release(cx.tmp, mark); return; }
+    const int ev_cap = tags ? line_ev_cap(r.L) * scale : 0;
+    int32_t *ev = tags ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)ev_cap) : nullptr;
+    if (!la || !cur_buf || !rec_buf || (tags && !ev)) { arena_release(cx.tmp, mark); return; }
+    la->ev = ev; la->ev_cap = ev_cap;
     for (int j = 0; j < F.n; ++j) {
         if (!fill_line(r, F, j, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX)) break;
         out_line(cx, o, *la);
@@ -207,7 +230,8 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
     if (skip) { cx.status |= ST_UNSUPPORTED; r.H = 0; r.seed_out = 0; }
     const int H = r.H;
     // read-lifetime allocations
-    const int out_cap = 64 + 12 * r.L * a.scale;
+    const int tags = a.in.tags & LAMSA_HP_TAG_MISMATCHES;
+    const int out_cap = (int)read_out_cap(r.L, a.scale, tags);
     OutBuf o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);
     r.rc_read = (uint8_t *)arena_alloc(cx, (size_t)r.L + 16);
@@ -240,7 +264,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
             FLines F;
             const bool ok1 = chain_first(r, F);
             HP_STAMP(1);
-            if (ok1 && F.n > 0) { o.w[n0_pos] = F.n; fill_round(r, F, o, &G, reg_cap, a.scale); }
+            if (ok1 && F.n > 0) { o.w[n0_pos] = F.n; fill_round(r, F, o, &G, reg_cap, a.scale, tags); }
             HP_STAMP(2);
             arena_release(cx.tmp, mark);
         }
@@ -251,7 +275,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
             FLines F;
             const bool ok2 = chain_remain(r, G, F);
             HP_STAMP(3);
-            if (ok2 && F.n > 0) { o.w[n1_pos] = F.n; fill_round(r, F, o, nullptr, 0, a.scale); }
+            if (ok2 && F.n > 0) { o.w[n1_pos] = F.n; fill_round(r, F, o, nullptr, 0, a.scale, tags); }
             HP_STAMP(4);
             arena_release(cx.tmp, mark);
         }

@@ -337,12 +337,12 @@ static int grow(lamsa_hp_handle *h, DevBuf &b, size_t bytes)
     return b.ensure(bytes);
 }
 
-static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale)
-{   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base), and the
-    // direction matrix of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.  Reads that need more
-    // flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
+static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale, int tags)
+{   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base; 24 more with the
+    // mismatch lists of LAMSA_HP_TAG_MISMATCHES), and the direction matrix of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
+    // Reads that need more flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
     const size_t z = (2 * (size_t)P.band_w + 128) * ((size_t)L + 256);
-    return al256(((size_t)256 << 10) + (size_t)scale * 128 * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
+    return al256(((size_t)256 << 10) + (size_t)scale * (tags ? 152 : 128) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
 }
 
 // validate `B`, build its processing order and sort index, copy it into slot `T` on the copy stream
@@ -552,7 +552,8 @@ static PhasedLayout phased_layout(int n, int64_t n_hits, int64_t n_bases, int64_
     Y.bytes = off;
     return Y;
 }
-static int64_t main_stream_cap(int n, int64_t n_bases) { return 1024 + (int64_t)n * 256 + 4 * n_bases; }
+// words of a batch's result stream; the mismatch lists (LAMSA_HP_TAG_MISMATCHES) are at most one word per aligned base and a count per record
+static int64_t main_stream_cap(int n, int64_t n_bases, int tags) { return 1024 + (int64_t)n * 256 + 4 * n_bases + (tags ? (int64_t)n * 128 + 2 * n_bases : 0); }
 
 // The main pass of the batch in slot `T` as the five launches of hp_phase.h, with the launch resources of slot `Ln`.
 // scratch of a wave of each kind of launch (all launches of a batch share one allocation, one after the other): the chaining launches keep
@@ -584,12 +585,12 @@ static SlabPlan slab_plan(lamsa_hp_handle *h, int max_L, int max_H, bool shared 
     // itself, a lane-DP group's buffers.  Wave jobs: an ordinary slab takes the junctions and the end extensions of a few thousand rows; the
     // direction matrix of the longest end extension (the whole read long) lives in one of the big slabs that only the first waves own.
     Q.chain = al256(((size_t)256 << 10) + 128 * (size_t)max_L + 424 * (size_t)max_H);
-    Q.fill = al256(((size_t)256 << 10) + 128 * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
+    Q.fill = al256(((size_t)256 << 10) + (h->result_tags ? 152 : 128) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
     { static const int kb = getenv("LAMSA_HP_WJ_SLAB_KB") ? atoi(getenv("LAMSA_HP_WJ_SLAB_KB")) : 0;    // diagnostic
       Q.wj = ((size_t)(kb > 0 ? kb : 1024) << 10) + 33 * 256; }
     Q.wjb = al256((size_t)wj_need(&P, WJ_HEAD, max_L, max_L + 2 * P.hash_step + 64) + ((size_t)64 << 10)) + 33 * 256;
     if (Q.wjb < Q.wj) Q.wjb = Q.wj;
-    if (g_nowave) Q.fill = std::max(Q.fill, slab_bytes_for(P, max_L, max_H, 1));            // (diagnostics: the fill runs every DP itself)
+    if (g_nowave) Q.fill = std::max(Q.fill, slab_bytes_for(P, max_L, max_H, 1, h->result_tags));            // (diagnostics: the fill runs every DP itself)
     if (h->scratch_limit) { const size_t lim = al256(h->scratch_limit); Q.chain = std::min(Q.chain, lim); Q.fill = std::min(Q.fill, lim); Q.wj = std::min(Q.wj, lim); Q.wjb = std::min(Q.wjb, lim); }
     int pc = 0, pf = 0, pd = 0, pw = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, g_chain_shapes[shape].k1, 64, 0) != hipSuccess || pc < 1) pc = 4 * g_chain_shapes[shape].waves_per_simd;
@@ -629,7 +630,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
     PhaseArgs a;
     a.P = h->para;
     a.ref.pac = h->d_pac; a.ref.l_pac = h->l_pac; a.ref.n_seqs = h->n_seqs; a.ref.seq_off = h->d_seq_off; a.ref.seq_len = h->d_seq_len;
-    a.in = T.in;
+    a.in = T.in; a.in.tags = h->result_tags;
     a.out.read_out_off = O.off(); a.out.read_out_len = O.len(n); a.out.read_status = O.st(n); a.out.read_tbases = O.tb(n); a.out.read_work = O.work(n); a.out.stream = O.stream(n);
     a.out.stream_cap = O.stream_cap; a.out.cursor = (unsigned long long *)((char *)Ln.misc.p + 64); a.out.diag = O.diag(n);
     a.slab = (char *)Ln.slab.p; a.slab_per_wave = Q.chain; a.slab_fill = Q.fill; a.slab_wj = Q.wj; a.slab_wjb = Q.wjb; a.wjb_off = Q.wjb_off; a.n_wjb = Q.n_wjb; a.sort_pb = T.sort_pb; a.sort_cb = T.sort_cb;
@@ -689,7 +690,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
 static int launch_align(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, OutDev &O, const int32_t *d_order, int n_units, int scale, int max_L, int max_H,
                         hipEvent_t e0, hipEvent_t e1, bool wait)
 {
-    size_t slab_per_wave = slab_bytes_for(h->para, max_L, max_H, scale);
+    size_t slab_per_wave = slab_bytes_for(h->para, max_L, max_H, scale, h->result_tags);
     if (scale == 1 && h->scratch_limit && slab_per_wave > h->scratch_limit) slab_per_wave = al256(h->scratch_limit);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_align_batch, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
@@ -701,7 +702,7 @@ static int launch_align(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, Ou
     AlignArgs a;
     a.P = h->para;
     a.ref.pac = h->d_pac; a.ref.l_pac = h->l_pac; a.ref.n_seqs = h->n_seqs; a.ref.seq_off = h->d_seq_off; a.ref.seq_len = h->d_seq_len;
-    a.in = T.in;
+    a.in = T.in; a.in.tags = h->result_tags;
     a.out.read_out_off = O.off(); a.out.read_out_len = O.len(n); a.out.read_status = O.st(n); a.out.read_tbases = O.tb(n); a.out.read_work = O.work(n); a.out.stream = O.stream(n);
     a.out.stream_cap = O.stream_cap; a.out.cursor = (unsigned long long *)((char *)Ln.misc.p + 64); a.out.diag = nullptr;
     a.slab = (char *)Ln.slab.p; a.slab_per_wave = slab_per_wave; a.counter = (int32_t *)Ln.misc.p;
@@ -740,7 +741,7 @@ static int start_main(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln)
     if (rc) return rc;
     const int n = T.n_reads;
     if (n == 0) return LAMSA_HP_OK;
-    if (Ln.out1.ensure(n, main_stream_cap(n, T.n_bases))) { h->err = "hipMalloc(out)"; return LAMSA_HP_ENOMEM; }
+    if (Ln.out1.ensure(n, main_stream_cap(n, T.n_bases, h->result_tags))) { h->err = "hipMalloc(out)"; return LAMSA_HP_ENOMEM; }
     Ln.phased = false;
     if (!g_mono) return launch_phased(h, S, T, Ln, Ln.out1, Ln.e0, Ln.e1);
     return launch_align(h, S, T, Ln, Ln.out1, T.d_order, n, 1, T.max_L, T.max_H, Ln.e0, Ln.e1, false);
@@ -792,7 +793,7 @@ static int finish_main(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, lam
     unsigned long long used2 = 0;
     if (!again.empty()) {
         int mL = 0, mH = 0; int64_t cap2 = 1024;
-        for (int r : again) { mL = std::max(mL, T.h_len[r]); mH = std::max(mH, T.h_H[r]); cap2 += 64 + 12LL * 8 * T.h_len[r]; }
+        for (int r : again) { mL = std::max(mL, T.h_len[r]); mH = std::max(mH, T.h_H[r]); cap2 += read_out_cap(T.h_len[r], 8, h->result_tags); }
         if (grow(h, S->out2.buf, 4 * (size_t)cap2 + 256) || S->out2.host.ensure(OutDev::hdr(n) + 256) || grow(h, S->retry_list, 4 * again.size())) { h->err = "hipMalloc(retry)"; return LAMSA_HP_ENOMEM; }
         S->out2.stream_cap = cap2;
         HIPCHK(h, hipMemcpyAsync(S->retry_list.p, again.data(), 4 * again.size(), hipMemcpyHostToDevice, Ln.cs), LAMSA_HP_EKERNEL);
@@ -933,7 +934,7 @@ extern "C" int lamsa_hp_reserve(lamsa_hp_handle *h, int32_t n_reads, int64_t n_b
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight"; return LAMSA_HP_EINVAL; }
     const SlabPlan Q = slab_plan(h, max_read_len, max_hits_per_read, false, chain_shape(h->para, n_reads, n_bases));
-    const int64_t cap = main_stream_cap(n_reads, n_bases);
+    const int64_t cap = main_stream_cap(n_reads, n_bases, h->result_tags);
     const PhasedLayout Y = phased_layout(n_reads, n_hits, n_bases, cap);
     // the packed input of a batch (upload_into): every array plus its 256-byte alignment, both CIGAR forms' staging included
     const size_t in_bytes = (size_t)n_bases + 16 * (size_t)n_reads * 4 + 32 * ((size_t)n_hits + n_reads) + 8 * (size_t)n_hits + 5 * (size_t)n_cig + 64 * 256 + 4096;
@@ -952,5 +953,14 @@ extern "C" int lamsa_hp_set_scratch_limit(lamsa_hp_handle *h, size_t bytes)
 {
     if (!h || (bytes && bytes < ((size_t)64 << 10))) return LAMSA_HP_EINVAL;
     h->scratch_limit = bytes;
+    return LAMSA_HP_OK;
+}
+
+extern "C" int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags)
+{
+    if (!h || (flags & ~LAMSA_HP_TAG_MISMATCHES)) return LAMSA_HP_EINVAL;
+    AlignState *S = state_of(h);
+    if (S->n_fifo || S->n_res) { h->err = "batches are in flight: collect them first"; return LAMSA_HP_EINVAL; }
+    h->result_tags = flags;
     return LAMSA_HP_OK;
 }

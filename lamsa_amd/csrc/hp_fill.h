@@ -21,9 +21,11 @@ namespace hp {
 
 struct Rec {                     // res_t, frag_check.h:46-59
     int64_t offset, refend; int32_t chr, nstrand, readend, score, NM; CigV cig;
+    int32_t *mm; int32_t n_mm;   // with LineRes::ev: the record's mismatches (ref_off << 2 | base), a view into ev like the CIGARs
 };
 struct LineRes {                 // line_aln_res, frag_check.h:61-73
     int line_score, tol_score, tol_NM, cur_res_n;
+    int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (LAMSA_HP_TAG_MISMATCHES), or nullptr
     Rec rec[HP_REC_MAX];
 };
 
@@ -999,8 +1001,12 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
 {
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
+    // with la.ev every mismatch is also written down, in reference order: the records' lists lie back to back in la.ev
+    HP_G int32_t *ev = (HP_G int32_t *)la.ev;
+    int ev_n = 0;
     for (int m = 0; m <= la.cur_res_n; ++m) {
         Rec &rec = la.rec[m];
+        const int ev0 = ev_n;
         const size_t mark = arena_mark(cx.tmp);
         int32_t ref_len = cig_reflen(rec.cig.c, rec.cig.n);
         uint8_t *ref = (uint8_t *)arena_alloc(cx, (size_t)(ref_len > 0 ? ref_len : 0) + 16);
@@ -1070,6 +1076,24 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
                     }
 #pragma unroll
                     for (int u = 0; u < RA_U; ++u) { WAVE_FOR(l) { mm[l] += b[u][l] != 0 && a[u][l] != b[u][l] - 256; } }
+                    if (ev) {
+                        // each mismatching lane's slot is the number of mismatches of the lanes below it (a prefix over the flags of
+                        // the pass); passes in base order, so a record's list comes out sorted by reference offset
+#pragma unroll
+                        for (int u = 0; u < RA_U; ++u) {
+                            const wv::Lane<int> dv = wv::gather(delta, e[u]);
+                            wv::Lane<int> f, slot;
+                            WAVE_FOR(l) { f[l] = b[u][l] != 0 && a[u][l] != b[u][l] - 256; slot[l] = f[l]; }
+                            const int cnt = __builtin_popcountll(wv::ballot(f));
+                            if (cnt == 0) continue;
+                            wv::scan_add_excl(slot);
+                            WAVE_FOR(l) {
+                                const int k = ev_n + slot[l];
+                                if (f[l] && k < la.ev_cap) ev[k] = ((ref_i + q0 + 64 * u + l + dv[l]) << 2) | (b[u][l] - 256);
+                            }
+                            ev_n += cnt;
+                        }
+                    }
                 }
             }
             const int mms = wv::reduce_sum(mm);
@@ -1082,11 +1106,17 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
         if (bad || read_i != r.L || ref_i != ref_len) { cx.status |= ST_REFEXIT; return false; }
         rec.NM = n_mm + n_ie + n_de;
         rec.score = n_m * P->match - n_mm * P->mis - n_io * P->ins_gapo - n_ie * P->ins_gape - n_do * P->del_gapo - n_de * P->del_gape;
+        if (ev) {
+            if (ev_n > la.ev_cap) { cx.status |= ST_OVERFLOW; return false; }
+            rec.mm = la.ev + ev0; rec.n_mm = ev_n - ev0;
+        }
         if (rec.score < 0) {                                          // record deleted, :839-844 (CIGARs are views: no copy needed)
+            ev_n = ev0;                                               // its mismatch list goes with it (it is the last one written)
             for (int i = m + 1; i <= la.cur_res_n; ++i) la.rec[i - 1] = la.rec[i];
             --m; --la.cur_res_n;
         } else { la.tol_score += rec.score; la.tol_NM += rec.NM; }
     }
+    if (ev) wv::sync();
     if (la.cur_res_n < 0) la.tol_score = -1;
     else la.tol_score -= la.cur_res_n * P->split_pen;
     return true;

@@ -39,6 +39,7 @@ struct lamsa_hp_handle {
     std::vector<int32_t> h_score, h_qle, h_tle, h_status;
     float kernel_ms[24] = {0};
     size_t scratch_limit = 0;      // lamsa_hp_set_scratch_limit
+    int result_tags = 0;           // lamsa_hp_set_result_tags: LAMSA_HP_TAG_* items of the result streams of later batches
     std::string err;
 };
 

@@ -12,6 +12,9 @@
 // (include/lamsa_hp.h).  Stage (4), the BWT rescue of short uncovered regions (src/bwt_aln.c), is in rescue.cpp.
 #include "lamsa_host.h"
 #include "rescue.h"
+// referenced weakly: a C-ABI without it (the tests' CPU emulation of the library) leaves it null, and --MD then derives the mismatch
+// lists on the host with the walk of the stage-4 records (rec_aux); the product's library always has it and the device lists them
+#pragma weak lamsa_hp_set_result_tags
 #include <algorithm>
 #include <atomic>
 #include <cctype>
@@ -579,7 +582,7 @@ static void merge_batches(Batch &B, std::vector<Batch> &parts, int threads)
 }
 
 // ------------------------------------------------------------------ result stream -> records
-void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R)
+void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm)
 {
     // (R may hold an earlier read's result: its lines, records and CIGAR vectors are reused, not freed and allocated again)
     R.stage[2].clear();
@@ -596,6 +599,8 @@ void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R)
                 r.offset = (int64_t)(((uint64_t)(uint32_t)s[i + 1] << 32) | (uint32_t)s[i]); r.chr = s[i + 2]; r.nstrand = s[i + 3]; r.score = s[i + 4]; r.NM = s[i + 5];
                 const int cn = s[i + 6]; i += 7;
                 r.cigar.assign(s + i, s + i + cn); i += cn;
+                if (with_mm) { const int nm = s[i]; r.mm.assign(s + i + 1, s + i + 1 + nm); i += 1 + nm; }
+                else r.mm.clear();
                 // covered read interval, push_reg_res src/lamsa_aln.c:571-595
                 if (r.cigar.empty()) { r.reg_beg = 1; r.reg_end = read_len; continue; }
                 const int32_t c0 = r.cigar.front(), c1 = r.cigar.back();
@@ -604,6 +609,19 @@ void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R)
             }
         }
     }
+}
+
+// the mismatch lists of rounds 1 and 2 from the read and the .pac, for a library without lamsa_hp_set_result_tags
+static void host_mismatches(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix)
+{
+    std::vector<uint8_t> rc;
+    for (int st = 0; st < 2; ++st)
+        for (Line &ln : R.stage[st])
+            for (Rec &r : ln.rec) {
+                if (r.nstrand == 0 && rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
+                AuxCounts k;
+                if (!rec_aux(ix, r.nstrand ? bseq : rc.data(), read_len, r, k)) R.status |= LAMSA_HP_ST_REFEXIT;
+            }
 }
 
 // a stable sort that allocates nothing for the handful of elements a read has (std::stable_sort asks for a buffer every time)
@@ -741,12 +759,51 @@ static inline void append_cigar(std::string &o, const std::vector<int32_t> &cig,
     o.resize((size_t)(p - o.data()));
 }
 
+// MD:Z of a record (SAM spec form): its CIGAR walked against its mismatch list, the bases of deletions from the index's .pac.  Where the
+// reference has N the .pac holds a substituted base (as the reference's index does); MD shows that base, the one NM was counted against.
+static void append_md(std::string &o, const Rec &r, const Index &ix)
+{
+    static const char B[] = "ACGT";
+    const int64_t k0 = ix.off[(size_t)r.chr - 1] + r.offset - 1;      // .pac coordinate of POS
+    int64_t ref = 0; int run = 0; size_t e = 0;
+    for (int32_t w : r.cigar) {
+        const int op = w & 0xf, len = w >> 4;
+        if (op == 0) {
+            const int64_t end = ref + len;
+            for (; e < r.mm.size() && (r.mm[e] >> 2) < end; ++e) {
+                const int64_t p = r.mm[e] >> 2;
+                run += (int)(p - ref); append_int(o, run); o.push_back(B[r.mm[e] & 3]);
+                run = 0; ref = p + 1;
+            }
+            run += (int)(end - ref); ref = end;
+        } else if (op == 2) {
+            append_int(o, run); run = 0; o.push_back('^');
+            for (int j = 0; j < len; ++j, ++ref) { const int64_t k = k0 + ref; o.push_back(B[ix.pac[(size_t)(k >> 2)] >> ((~k & 3) << 1) & 3]); }
+        }                                                           // I, S, H: nothing of the reference
+    }
+    append_int(o, run);
+}
+
 void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index &ix, const Options &opt)
 {
     static const char OPS[] = "MIDNSHP=XB", OPS_HC[] = "MIDNHHP=XB";
     const int read_len = (int)rd.seq.size();
     const bool with_qual = rd.has_qual && opt.comm;
     int all = 0; bool prim = false;
+    // --SA: the records printed for this read, in print order, and the SA:Z entry of each (rname,pos,strand,CIGAR,mapQ,NM; -- soft clips
+    // even where the line itself is hard-clipped)
+    std::vector<std::string> sa;
+    if (opt.tag_sa) {
+        for (int st = 0; st < 3; ++st)
+            for (const Line &la : R.stage[st]) {
+                if (la.merg_x != 1) continue;
+                for (const Rec &r : la.rec) {
+                    std::string x = ix.name[(size_t)r.chr - 1]; x.push_back(','); append_int(x, (long long)r.offset); x.push_back(','); x.push_back("-+"[r.nstrand]); x.push_back(',');
+                    append_cigar(x, r.cigar, OPS); x.push_back(','); append_int(x, (int)la.mapQ); x.push_back(','); append_int(x, r.NM); x.push_back(';');
+                    sa.push_back(std::move(x));
+                }
+            }
+    }
     if (o.capacity() - o.size() < 4 * (size_t)read_len + 4096) o.reserve(o.size() + std::max<size_t>(o.size() / 2, 8 * (size_t)read_len + 65536));      // grown in large steps, not per append
     for (int st = 0; st < 3; ++st)
         for (const Line &la : R.stage[st]) {
@@ -778,6 +835,8 @@ void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index 
                         o.push_back(','); append_int(o, xr.NM); o.push_back(';');
                     }
                 }
+                if (opt.tag_md) { o += "\tMD:Z:"; append_md(o, r, ix); }
+                if (sa.size() > 1) { o += "\tSA:Z:"; for (size_t k = 0; k < sa.size(); ++k) if (k != (size_t)all - 1) o += sa[k]; }
                 o.push_back('\n');
             }
         }
@@ -1020,6 +1079,13 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     if (rc != LAMSA_HP_OK) for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh);
     const int G = (int)std::max<size_t>(1, hs.size());
     if (rc != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] no usable MI355X / HIP device (lamsa_hp_create: %d); this build has no CPU path\n", rc); return 2; }
+    // --MD: every handle lists the mismatches of its records in the result stream
+    const bool dev_mm = opt.tag_md && lamsa_hp_set_result_tags != nullptr;
+    for (lamsa_hp_handle *hh : hs) {
+        if (!dev_mm) break;
+        const int e = lamsa_hp_set_result_tags(hh, LAMSA_HP_TAG_MISMATCHES);
+        if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_set_result_tags failed: %d %s\n", e, lamsa_hp_last_error(hh)); for (lamsa_hp_handle *x : hs) lamsa_hp_destroy(x); return 2; }
+    }
     // stage (4): needs the reference's FM index files and a second handle for its DP batches (a handle is single-threaded)
     FmIndex fm; lamsa_hp_handle *h_dp = nullptr; bool rescue = false; long n_rescue_jobs = 0;
     if (P.bwt_max_len > 0 && !opt.parse_only) {
@@ -1253,7 +1319,8 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             for (int r = r0; r < r1; ++r) {
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
-                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R);
+                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm);
+                if (opt.tag_md && !dev_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
                 if (rescue && R.status == 0) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
             }
         });

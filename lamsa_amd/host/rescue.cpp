@@ -390,6 +390,29 @@ static inline void push_n(std::vector<int32_t> &c, const int32_t *w, int n)
     for (; j < n; ++j) c.push_back(w[j]);
 }
 
+bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts &k)
+{
+    int ref_len = ref_in_cigar(r.cigar);
+    std::vector<uint8_t> ref;
+    bool ok = fetch_ref(ix, r.chr, r.offset - 1, &ref_len, ref);
+    int ref_i = 0, read_i = 0;
+    r.mm.clear();
+    for (size_t i = 0; ok && i < r.cigar.size(); ++i) {
+        const int op = r.cigar[i] & 0xf, len = r.cigar[i] >> 4;
+        if (op == 0) {
+            if (read_i + len > read_len || ref_i + len > ref_len) { ok = false; break; }
+            int mm = 0;
+            for (int j = 0; j < len; ++j, ++read_i, ++ref_i) if (rd[read_i] != ref[(size_t)ref_i]) { ++mm; r.mm.push_back(ref_i << 2 | ref[(size_t)ref_i]); }
+            k.n_m += len - mm; k.n_mm += mm;
+        }
+        else if (op == 1) { read_i += len; k.n_ie += len; ++k.n_io; }
+        else if (op == 2) { ref_i += len; k.n_de += len; ++k.n_do; }
+        else if (op == 4) read_i += len;
+        else ok = false;
+    }
+    return ok && read_i == read_len && ref_i == ref_len;
+}
+
 void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp)
 {
     std::vector<Line> &out = R.stage[2];
@@ -425,21 +448,10 @@ void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index
             if (rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
             rd = rc.data();
         }
-        int ref_len = ref_in_cigar(r.cigar);
-        std::vector<uint8_t> ref;
-        bool ok = fetch_ref(ix, r.chr, r.offset - 1, &ref_len, ref);
-        int ref_i = 0, read_i = 0, n_mm = 0, n_m = 0, n_io = 0, n_ie = 0, n_do = 0, n_de = 0;
-        for (size_t i = 0; ok && i < r.cigar.size(); ++i) {
-            const int op = r.cigar[i] & 0xf, len = r.cigar[i] >> 4;
-            if (op == 0) { if (read_i + len > read_len || ref_i + len > ref_len) { ok = false; break; } int mm = 0; for (int j = 0; j < len; ++j) mm += rd[read_i++] != ref[(size_t)ref_i++]; n_m += len - mm; n_mm += mm; }
-            else if (op == 1) { read_i += len; n_ie += len; ++n_io; }
-            else if (op == 2) { ref_i += len; n_de += len; ++n_do; }
-            else if (op == 4) read_i += len;
-            else ok = false;
-        }
-        if (!ok || read_i != read_len || ref_i != ref_len) { R.status |= LAMSA_HP_ST_REFEXIT; return; }      // the reference exits with "Unmatched length"
-        r.NM = n_mm + n_ie + n_de;
-        r.score = n_m * P.match - n_mm * P.mis - n_io * P.ins_gapo - n_ie * P.ins_gape - n_do * P.del_gapo - n_de * P.del_gape;
+        AuxCounts k;
+        if (!rec_aux(ix, rd, read_len, r, k)) { R.status |= LAMSA_HP_ST_REFEXIT; return; }      // the reference exits with "Unmatched length"
+        r.NM = k.n_mm + k.n_ie + k.n_de;
+        r.score = k.n_m * P.match - k.n_mm * P.mis - k.n_io * P.ins_gapo - k.n_ie * P.ins_gape - k.n_do * P.del_gapo - k.n_de * P.del_gape;
         int cur_res_n = 0;
         if (r.score < 0) cur_res_n = -1; else { la.tol_score += r.score; la.tol_NM += r.NM; }
         if (cur_res_n < 0) la.tol_score = -1; else la.tol_score -= cur_res_n * P.split_pen;

@@ -52,6 +52,13 @@ void rescue_plan(const ReadResult &R, const uint8_t *bseq, int read_len, const I
 
 struct DpResults { const int32_t *score, *qle, *tle; const int64_t *cig_off; const int32_t *cigar; int64_t base; };   // base: first job of this thread's list
 
+// lamsa_res_aux's walk over one record (src/frag_check.c:793-848): `rd` = the read's base codes on the record's strand (reverse
+// complement for '-'), reference bases from the index's .pac.  Counts what NM and AS are made of and lists the record's mismatches in
+// r.mm as the device does (ref_off << 2 | base, LAMSA_HP_TAG_MISMATCHES).  false: the CIGAR does not fit the read or the contig (the
+// reference exits with "Unmatched length").
+struct AuxCounts { int n_mm = 0, n_m = 0, n_io = 0, n_ie = 0, n_do = 0, n_de = 0; };
+bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts &k);
+
 // finish: DP results -> R.stage[2]
 void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp);
 

@@ -58,7 +58,9 @@ EXPORTS = ("lamsa_hp_para_init", "lamsa_hp_para_finish", "lamsa_hp_create", "lam
            "lamsa_hp_last_error", "lamsa_hp_dp_batch", "lamsa_hp_last_kernel_ms", "lamsa_hp_set_scratch_limit",
            "lamsa_hp_align_batch", "lamsa_hp_upload_batch", "lamsa_hp_run_uploaded",
            "lamsa_hp_submit_batch", "lamsa_hp_collect_batch", "lamsa_hp_host_alloc", "lamsa_hp_host_free",
-           "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve")
+           "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve", "lamsa_hp_set_result_tags")
+
+TAG_MISMATCHES = 1      # LAMSA_HP_TAG_MISMATCHES: every record of the result stream also lists its mismatches
 
 _lib = None
 
@@ -115,6 +117,8 @@ def load_library(path=None):
         L.lamsa_hp_start_uploaded.restype = C.c_int
         L.lamsa_hp_finish_uploaded.argtypes = [C.c_void_p, C.POINTER(HpResult)]
         L.lamsa_hp_finish_uploaded.restype = C.c_int
+        L.lamsa_hp_set_result_tags.argtypes = [C.c_void_p, C.c_int]
+        L.lamsa_hp_set_result_tags.restype = C.c_int
         _lib = L
     return _lib
 
@@ -181,6 +185,13 @@ class LamsaHp:
         rc = self.L.lamsa_hp_set_scratch_limit(self._h, int(nbytes))
         if rc != 0:
             raise RuntimeError("lamsa_hp_set_scratch_limit failed: %d" % rc)
+
+    def set_result_tags(self, flags):
+        """Optional items of the result streams of later batches (TAG_MISMATCHES: after its CIGAR words every record carries
+        n_mm and n_mm words ref_off << 2 | base); 0 = none, the default."""
+        rc = self.L.lamsa_hp_set_result_tags(self._h, int(flags))
+        if rc != 0:
+            raise RuntimeError("lamsa_hp_set_result_tags failed: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
 
     def last_kernel_ms(self, which=0):
         return float(self.L.lamsa_hp_last_kernel_ms(self._h, which))
