@@ -88,7 +88,8 @@ static const ChainShape g_chain_shapes[3] = {
 __global__ __launch_bounds__(64, HP_FILL_WAVES_PER_SIMD) void k_fill(const PhaseArgs *ap, int round)
 {
     const PhaseArgs &a = *ap;
-    __shared__ int32_t lds[HP_LDS_WORDS];            // this wave's DP rows, query window and direction matrix (hp_ksw.h)
+    __shared__ alignas(16) int32_t lds[HP_LDS_WORDS + PH_CTX_BYTES / 4];       // this wave's DP rows, query window and direction matrix (hp_ksw.h); behind them the read context (hp_phase.h)
+    ReadCtx &r = *(ReadCtx *)(lds + HP_LDS_WORDS);
     int n = 0;
     for (int b = 0; b < PH_NBUCKET; ++b) n += a.ctl->bucket_n[round][b];
     n = wv::uni(n);
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(64, HP_FILL_WAVES_PER_SIMD) void k_fill(const Phase
         int b = 0;
         while (b < PH_NBUCKET - 1 && g >= a.ctl->bucket_n[round][b]) { g -= a.ctl->bucket_n[round][b]; ++b; }     // costliest class first
         const int u = wv::uni(a.bucket_q[((size_t)round * PH_NBUCKET + b) * a.unit_cap + g]);
-        phase_fill(a, round, u, blockIdx.x, (HP_L int32_t *)lds);
+        phase_fill(a, round, u, blockIdx.x, (HP_L int32_t *)lds, r);
     }
     drain_stamp(a, 1 + 2 * round);
 }
@@ -113,6 +114,8 @@ __global__ __launch_bounds__(64, HP_FILL_WAVES_PER_SIMD) void k_fill(const Phase
 __global__ __launch_bounds__(64, HP_LIST_WAVES_PER_SIMD) void k_filllist(const PhaseArgs *ap, int round)
 {
     const PhaseArgs &a = *ap;
+    __shared__ alignas(16) int32_t lds[PH_CTX_BYTES / 4];       // the read context (hp_phase.h); the listing uses no other LDS (lds_words 0)
+    ReadCtx &r = *(ReadCtx *)lds;
     int n = 0;
     for (int b = 0; b < PH_NBUCKET; ++b) n += a.ctl->bucket_n[round][b];
     n = wv::uni(n);
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(64, HP_LIST_WAVES_PER_SIMD) void k_filllist(const P
         int b = 0;
         while (b < PH_NBUCKET - 1 && g >= a.ctl->bucket_n[round][b]) { g -= a.ctl->bucket_n[round][b]; ++b; }
         const int u = wv::uni(a.bucket_q[((size_t)round * PH_NBUCKET + b) * a.unit_cap + g]);
-        phase_filllist(a, round, u, blockIdx.x, (HP_L int32_t *)nullptr);
+        phase_filllist(a, round, u, blockIdx.x, (HP_L int32_t *)lds, r);
     }
 }
 // the lane-per-job DP over the round's queues (hp_lanedp.h): 64 jobs per wave, rows of HP_LJ_QSMALL cells per lane in LDS
@@ -562,7 +565,7 @@ static int64_t main_stream_cap(int n, int64_t n_bases, int tags) { return 1024 +
 struct SlabPlan { size_t chain, fill, wj, wjb, wjb_off; int w_chain, w_fill, w_dp, w_wj, n_wjb, shape; size_t bytes; };
 // shared: another batch's launches are in flight on the handle's other stream.  The launches are persistent grids; at full size the earlier
 // batch's grid owns every wave slot and the later one only gets what its tail leaves.  The DP launch is bound by instruction issue (VALU port
-// 78 % busy, profiles/r04_ont10k_pmc.json) and the chaining / fill launches by memory latency (wait 74-89 %, VALU 26-38 %): with every grid
+// 100 % busy, profiles/r04_ont10k_pmc.json) and the chaining / fill launches by memory latency (wait 73-85 %, VALU 32-38 %): with every grid
 // capped at half a CU's slots the launches of the two batches run side by side on the same CUs, one filling the issue slots the other leaves
 // idle -- measured 357 k reads/s against 345 k with full grids (profiles/r04_overlap.txt).  A batch that runs alone gets the whole CU.
 // which shape of the chaining kernels suits the batch: the hits at a read's true locus are at most one per seed -- about two in three of
@@ -660,7 +663,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
     if (list) {
         hipLaunchKernelGGL(k_filllist, dim3(w_fill), dim3(64), 0, s, da, 0);
         HIPCHK(h, hipEventRecord(Ln.ep[5], s), LAMSA_HP_EKERNEL);
-        if (!g_nowave) hipLaunchKernelGGL(k_filldp_wave, dim3(w_wj), dim3(64), 0, s, da, 0);       // the long jobs first: the short ones fill the SIMDs its tail leaves idle
+        if (!g_nowave) hipLaunchKernelGGL(k_filldp_wave, dim3(w_wj), dim3(64), 0, s, da, 0);       // the long jobs first; the lane-per-job launch follows on the same stream (the two do not overlap)
         HIPCHK(h, hipEventRecord(Ln.ep[6], s), LAMSA_HP_EKERNEL);
         if (!g_nolane) hipLaunchKernelGGL(k_filldp_small, dim3(w_dp), dim3(64), 0, s, da, 0);
     } else { HIPCHK(h, hipEventRecord(Ln.ep[5], s), LAMSA_HP_EKERNEL); HIPCHK(h, hipEventRecord(Ln.ep[6], s), LAMSA_HP_EKERNEL); }

@@ -111,17 +111,26 @@ HP_FN int cig_pushv_known(Ctx &cx, HP_G cig_t *dst, int &vn_io, int cap, int las
 // flanks grow once more.  The elements it walks over -- the tail of c1, the head of c2 -- are loaded once, 64 of each, one per lane,
 // and the walk reads lanes; the element a side stops in is shortened in a register and stored when the walk is over.  (Walked one at
 // a time out of HBM this routine was a quarter of the fill kernel: ~16 calls per line, each a chain of ~40 dependent round trips.)
-HP_NOINL bool merge_cigar_full(ReadCtx &r, CigV &c1, int64_t *c1_refend, int *c1_readend, int chr,
+HP_NOINL bool merge_cigar_full(ReadCtx &r_, CigV &c1_, int64_t *c1_refend, int *c1_readend, int chr,
                                const cig_t *_c2, int c2_n, int c2_reflen, int c2_readlen)
 {
     if (c2_n == 0) return true;
+    HP_STAT(26);
+    // Arguments of a non-inlined device routine arrive in vector registers; all of them are wave-uniform and most are needed again after
+    // the DP below: as they came they would sit in callee-saved vector registers, each one a store and a load through scratch per call
+    // (~18 calls per line of a noisy read).  Scalar registers cost a lane write instead.
+    ReadCtx &r = *(ReadCtx *)wv::uni64((long long)&r_);
+    CigV &c1 = *(CigV *)wv::uni64((long long)&c1_);
+    c1_refend = (int64_t *)wv::uni64((long long)c1_refend); c1_readend = (int *)wv::uni64((long long)c1_readend);
+    _c2 = (const cig_t *)wv::uni64((long long)_c2);
+    chr = wv::uni(chr); c2_n = wv::uni(c2_n); c2_reflen = wv::uni(c2_reflen); c2_readlen = wv::uni(c2_readlen);
     Ctx &cx = r.cx;
     HP_T0(tmf_);
-    const lamsa_hp_para *P = cx.P;
+    const lamsa_hp_para *P = (const lamsa_hp_para *)wv::uni64((long long)cx.P);
     // what is needed of the vector and of the record's ends, read once (they lie in memory: every later use would be a load behind the stores)
     HP_G cig_t *const c1c = (HP_G cig_t *)wv::uni64((long long)c1.c);
     const int n1_0 = wv::uni(c1.n), c1cap = wv::uni(c1.cap);
-    const int64_t refend0 = *c1_refend; const int readend0 = wv::uni(*c1_readend), read_L = wv::uni(r.L);
+    const int64_t refend0 = wv::uni64(*c1_refend); const int readend0 = wv::uni(*c1_readend), read_L = wv::uni(r.L);
     const uint8_t *const cur_read = (const uint8_t *)wv::uni64((long long)r.cur_read);
     const HP_G cig_t *g1 = c1c, *g2 = (const HP_G cig_t *)_c2;
     int vn = n1_0;
@@ -372,6 +381,7 @@ HP_INL int frag_steps_block(ReadCtx &r, const FLines &F, int frag, int i, int st
 
 HP_NOINL bool frag_extend_multi(ReadCtx &r, const FLines &F, int frag, Rec &res)
 {
+    HP_STAT(27);
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
     const int32_t *seed = F.fr_seed + F.fr_seed_off[frag];
@@ -435,6 +445,7 @@ struct SplitGeo {
 // DEL / INS / DUP branches (:475-546): the structural-variant cases, rare on ordinary reads
 HP_NOINL bool split_sv(ReadCtx &r, const SplitGeo &g, Rec &res)
 {
+    HP_STAT(28);
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
     const int hash_len = P->hash_len, s_qlen = g.s_qlen, dis = g.dis;
@@ -497,6 +508,7 @@ HP_NOINL bool split_sv(ReadCtx &r, const SplitGeo &g, Rec &res)
 // mismatch class with read bases between the seeds (:547-559): two-sided extension
 HP_NOINL bool split_mismatch(ReadCtx &r, const SplitGeo &g, Rec &res)
 {
+    HP_STAT(29);
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
     int s_tlen = g.s_qlen + g.dis;

@@ -1591,6 +1591,7 @@ HP_INL bool bi_near_diag(const lamsa_hp_para *P, int qlen, int tlen)
 // ksw_bi_extend (src/ksw.c:862-926): result replaces out; returns the "gap exists" flag
 HP_NOINL int ksw_bi_extend(Ctx &cx_, int qlen, Seq q, int tlen, Seq t, int lh0, int rh0, CigV &out_)
 {
+    HP_STAT(31);
     // Arguments of a non-inlined device function arrive in vector registers; everything here is wave-uniform, and what lives across the
     // calls below should sit in scalar registers (the DP routines use up to 55 of the 64 vector registers the fill kernel has per lane:
     // what the caller keeps in vector registers goes to scratch and back around every call).

@@ -170,6 +170,10 @@ constexpr bool ph_ctx_in_lds(int words, int waves_per_simd)
 {
     return 4 * waves_per_simd * (((size_t)words * 4 + PH_CTX_BYTES + 511) / 512 * 512) <= 160 * 1024;
 }
+// The fill launches (k_fill, k_filllist) keep theirs behind the DP rows: HP_LDS_WORDS + PH_CTX_BYTES / 4 words per wave, of which the DP
+// routines and the staging of frags_merge see only the first HP_LDS_WORDS (cx.lds_words).  Seven waves per SIMD must keep fitting the CU.
+static_assert(PH_CTX_BYTES % 512 == 0, "the LDS block of a wave is sized in units of 512 bytes");
+static_assert(28 * (4 * HP_LDS_WORDS + PH_CTX_BYTES) <= 160 * 1024, "DP rows + read context of 7 waves per SIMD must fit the CU's LDS");
 struct ChainOut { FLines F; FlStore fs; };     // what chain_first / chain_remain leave for units_push
 
 HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words, ReadCtx &r)
@@ -209,33 +213,53 @@ HP_NOINL void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
     meta_flag(a, rd, r);
 }
 
-// the same with a read context of the calling frame (the one-wave-at-a-time CPU emulation of the tests)
+// the same with a read context of the calling frame (the one-wave-at-a-time CPU emulation of the tests).  With -DHP_PH_CTX_SHARED
+// (CPU builds only) the overloads use ONE block that lives across calls, as a wave of the GPU does: every read, line and phase meets
+// what the previous one left in it, so a field that a phase reads without having set it shows up in the tests.
+#ifdef HP_PH_CTX_SHARED
+HP_INL ReadCtx &ph_frame_ctx()
+{
+    alignas(16) static thread_local unsigned char blk[PH_CTX_BYTES];
+    static thread_local bool born = false;
+    if (!born) { for (int i = 0; i < PH_CTX_BYTES; ++i) blk[i] = 0xa5; born = true; }       // never a block of zeros: a GPU wave's is not either
+    return *reinterpret_cast<ReadCtx *>(blk);
+}
+#define PH_FRAME_CTX(r) ReadCtx &r = ph_frame_ctx()
+#else
+#define PH_FRAME_CTX(r) ReadCtx r##_frame_; ReadCtx &r = r##_frame_
+#endif
 HP_FN void phase_chain1(const PhaseArgs &a, int rd, int wave_slot, HP_L int32_t *lds, int lds_words = HP_CHAIN_LDS_WORDS)
 {
-    ReadCtx r;
+    PH_FRAME_CTX(r);
     phase_chain1(a, rd, wave_slot, lds, lds_words, r);
 }
 
 // ---------------------------------------------------------------- fill: one line of one read
-HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds)
+// The read context of the fill launches exists once per wave as well: `r` is the wave's block of PH_CTX_BYTES in LDS behind the DP rows
+// (k_fill, k_filllist).  The other records whose address leaves the phase -- the line's fragments, the output words, the covered
+// intervals of get_reg -- are one FillLoc in the wave's arena, as LineRes is: one copy per wave in HBM, every lane reads the same line.
+struct FillLoc { FLines F; OutBuf o; Regs G; };
+
+HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds, ReadCtx &r)
 {
     UnitRec &U = a.units[(size_t)round * a.unit_cap + u];
     const int rd = U.read, line = U.line;
     RdMeta &M = a.meta[rd];
     if (*(volatile int32_t *)&M.status & ST_DEAD) return;       // the read is lost already (another line or phase failed)
     PH_T0();
-    ReadCtx r;
     read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_fill, a.slab_fill, lds, a.prof, HP_LDS_WORDS);
     pers_bind(r, a, rd);
     Ctx &cx = r.cx;
-    FLines F;
+    FillLoc *fl = (FillLoc *)arena_alloc(cx, sizeof(FillLoc));
+    if (!fl) { meta_flag(a, rd, r); return; }                   // (a slab is never below 64 KiB: not reached)
+    FLines &F = fl->F;
     F.n = M.fl_n[round]; F.nfrag = M.fl_nfrag[round];
     flines_bind(F, a.fl_base + M.fl_off[round], F.n, M.fl_tot[round]);
     F.jarena = a.job_base;
     const int cur_cap = 2 * r.L + 512;
     const bool tags = (a.in.tags & LAMSA_HP_TAG_MISMATCHES) != 0;
     const int out_cap = 64 + 12 * r.L + PH_REG_WORDS * HP_REC_MAX + (tags ? line_ev_words(r.L) : 0);
-    OutBuf o; o.n = 0; o.cap = out_cap;
+    OutBuf &o = fl->o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);
     r.rc_read = (uint8_t *)arena_alloc(cx, (size_t)r.L + 16);
     LineRes *la = (LineRes *)arena_alloc(cx, sizeof(LineRes));
@@ -250,7 +274,7 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
         if (ok) {
             out_line(cx, o, *la);
             if (round == 0 && la->tol_score >= 0) {                                // get_reg, lamsa_aln.c:597-605
-                Regs G; G.n = 0; G.m = 0;
+                Regs &G = fl->G; G.n = 0; G.m = 0;
                 const size_t mark = arena_mark(cx.tmp);
                 G.beg = (int32_t *)arena_alloc(cx, sizeof(int32_t) * 2 * HP_REC_MAX); G.end = G.beg ? G.beg + HP_REC_MAX : nullptr;
                 G.rb = (RegB *)arena_alloc(cx, sizeof(RegB) * 2 * HP_REC_MAX); G.re = G.rb ? G.rb + HP_REC_MAX : nullptr;
@@ -283,6 +307,12 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
     meta_flag(a, rd, r);
 }
 
+// the same with a read context of the calling frame (CPU emulation)
+HP_FN void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds)
+{
+    PH_FRAME_CTX(r);
+    phase_fill(a, round, u, wave_slot, lds, r);
+}
 
 // ---------------------------------------------------------------- fill, step 1: the DP jobs of the lines, computed ahead of the fill.
 // phase_filllist (one line per wave) lists the line's junctions of the mismatch class with read bases in between (split_mapping,
@@ -353,13 +383,12 @@ HP_INL bool end_geo(const ReadCtx &r, const FLines &F, int line, int strand, boo
     return G.ref_len > 0 && G.read_start >= 0 && G.read_start + G.read_len <= r.L;
 }
 
-HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds)
+HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds, ReadCtx &r)
 {
     UnitRec &U = a.units[(size_t)round * a.unit_cap + u];
     const int rd = U.read, line = U.line;
     RdMeta &M = a.meta[rd];
     if (*(volatile int32_t *)&M.status & ST_DEAD) return;
-    ReadCtx r;
     read_bind(r, a.P, a.ref, a.in, rd, a.slab + (size_t)wave_slot * a.slab_fill, a.slab_fill, lds, a.prof, 0);
     pers_bind(r, a, rd);
     const lamsa_hp_para *P = r.cx.P;
@@ -567,6 +596,13 @@ HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot
     r.flip = false;
     r.t_bases = tb;
     meta_flag(a, rd, r);
+}
+
+// the same with a read context of the calling frame (CPU emulation)
+HP_FN void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds)
+{
+    PH_FRAME_CTX(r);
+    phase_filllist(a, round, u, wave_slot, lds, r);
 }
 
 // group g of 64 jobs of the round's queues (the caller maps g to a queue and an offset)

@@ -179,6 +179,7 @@ HP_FN int indel_cigar(Ctx &cx, int ref_left, int read_left, int ref_right, int r
 // failure; `out` is cleared first like hash_split_map does (:652).
 HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int read_len, const uint8_t *ref_seq, int ref_len, int ref_offset)
 {
+    HP_STAT(30);
     const lamsa_hp_para *P = cx.P;
     const int hash_len = P->hash_len, hash_step = P->hash_step, split_len = P->split_pen;   // sic, :640
     int res = 0;

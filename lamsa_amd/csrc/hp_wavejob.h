@@ -6,7 +6,7 @@
 // frag_tail_bound_fix :656-707 -> ksw_extend_c, up to the whole read long).  None of them depends on the line's growing CIGAR -- only
 // merge_cigar (:251), which joins their results, is sequential -- so the listing launch (phase_filllist, hp_phase.h) writes them as job
 // records with the geometry the fill would compute, and this launch runs them one per wavefront, costliest first: a launch that is all
-// instruction issue (VALU port 78 % busy) beside a fill launch that is all memory latency (wait 89 %), instead of one kernel that is both; the
+// instruction issue (VALU port 100 % busy, profiles/r04_ont10k_pmc.json) before a fill launch that is all memory latency (wait 85 %), instead of one kernel that is both; the
 // direction matrix of the two-columns-per-lane routines lies in the wave's LDS where it fits (a junction of up to 80 rows).  The fill finds the
 // CIGARs in the job arena (FLines::jt / gt / ht) and goes on with merge_cigar; a job that was not listed, or whose buffers did not suffice, is
 // run by the fill as before.
