@@ -108,7 +108,7 @@ HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
 HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + (tags ? 4LL * L + 4 * HP_REC_MAX : 0)) * scale; }
 
 // frag_check over all lines of one round (frag_check.c:886-955) + get_reg (lamsa_aln.c:597) for round 1
-HP_NOINL void fill_round(ReadCtx &r, FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
+HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
 {
     Ctx &cx = r.cx;
     const size_t mark = arena_mark(cx.tmp);

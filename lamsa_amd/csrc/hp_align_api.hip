@@ -136,7 +136,7 @@ __global__ __launch_bounds__(64, 2) void k_filldp_small(const PhaseArgs *ap, int
     __shared__ int32_t lds[HP_LJ_LDS_WORDS(HP_LJ_QSMALL)];
     const PhaseArgs &a = *ap;
     int n = 0;
-    for (int b = 0; b < LJ_NBUCKET; ++b) n += ((a.ctl->lj_bucket_n[round][b] < a.lj_cap ? a.ctl->lj_bucket_n[round][b] : a.lj_cap) + 63) >> 6;
+    for (int b = 0; b < LJ_NBUCKET; ++b) n += (lj_queue_n(a, round, b) + 63) >> 6;
     n = wv::uni(n);
     for (;;) {
         int g = 0;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(64, 2) void k_filldp_small(const PhaseArgs *ap, int
         g = wv::uni(g);
         if (g >= n) break;
         int b = 0;
-        for (; b < LJ_NBUCKET - 1; ++b) { const int gb = ((a.ctl->lj_bucket_n[round][b] < a.lj_cap ? a.ctl->lj_bucket_n[round][b] : a.lj_cap) + 63) >> 6; if (g < gb) break; g -= gb; }
+        for (; b < LJ_NBUCKET - 1; ++b) { const int gb = (lj_queue_n(a, round, b) + 63) >> 6; if (g < gb) break; g -= gb; }
         phase_filldp(a, round, b, g * 64, blockIdx.x, (HP_L int32_t *)lds, HP_LJ_QSMALL);
     }
 }
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64, HP_WJ_WAVES_PER_SIMD) void k_filldp_wave(const 
     __shared__ int32_t lds[HP_WJ_LDS_WORDS];
     const PhaseArgs &a = *ap;
     int n = 0, n_big = 0;
-    for (int b = 0; b < WJ_NBUCKET; ++b) { const int k = a.ctl->wj_bucket_n[round][b] < a.wj_cap ? a.ctl->wj_bucket_n[round][b] : a.wj_cap; if (b < WJ_NBIG) n_big += k; else n += k; }
+    for (int b = 0; b < WJ_NBUCKET; ++b) { const int k = wj_queue_n(a, round, b); if (b < WJ_NBIG) n_big += k; else n += k; }
     n = wv::uni(n); n_big = wv::uni(n_big);
     bool own_big = (int)blockIdx.x < a.n_wjb;           // this wave owns a big slab: the jobs that need one first (they are the costliest)
     for (;;) {

@@ -1,6 +1,7 @@
 // hp_fill.h -- lines of fragments -> base-level alignment records on one wavefront
 // (reference src/frag_check.c, src/bntseq.c:465).
 //
+//   junction_geo, gap_geo, end_geo, contig_clip   where the DP of a junction / seed gap / end extension runs (shared with hp_phase.h)
 //   ref_fetch      <- pac2fa_core      bntseq.c:465  2-bit window unpacked by the 64 lanes
 //   merge_cigar    <- merge_cigar      frag_check.c:251
 //   frag_extend    <- frag_extend      :332
@@ -8,7 +9,10 @@
 //   head_fix/tail_fix <- frag_head_bound_fix / frag_tail_bound_fix  :576,:656
 //   res_split      <- lamsa_res_split  :712
 //   res_aux        <- lamsa_res_aux    :793  mismatch counting spread over the lanes
-//   fill_lines     <- frag_check       :856
+//   fill_line      <- frag_check       :856 (one line)
+// Where every DP of a line runs -- read interval, reference window, contig clipping, whether there is one at all -- is worked out by the
+// geometry section below and nowhere else: the fill and the listing launch that computes the DPs ahead (phase_filllist, hp_phase.h) call
+// the same routines, so a CIGAR found in a slot of FLines::jt / gt / ht was computed for the window the fill would have used.
 // Control flow is wave-uniform; sequences are never copied or reversed, DP routines read
 // them through strided views.  Where the reference exit(1)s the read is flagged
 // ST_REFEXIT and abandoned.
@@ -29,13 +33,120 @@ struct LineRes {                 // line_aln_res, frag_check.h:61-73
     Rec rec[HP_REC_MAX];
 };
 
+// ---------------------------------------------------------------- geometry of the DP jobs of a line
+// One routine per kind of job, shared by the fill (below) and the lister (phase_filllist).  None of them flags anything: the fill turns
+// "the reference exits" into ST_REFEXIT, the lister just does not list such a job.
+
+// pac2fa_core, bntseq.c:469-474: a window that starts outside the contig makes the reference exit (false); else its length is cut at the contig end
+HP_INL bool contig_clip(const RefView &ref, int chr, int64_t start0, int32_t &len)
+{
+    const int32_t clen = ref.seq_len[chr - 1];
+    if (start0 > clen || start0 < 0) return false;
+    if (start0 + len > clen) len = (int32_t)(clen - start0);
+    return true;
+}
+
+// Junction between fragments f1 and f2 (f2 follows f1 on the read): split_mapping :424-470 and the window of its mismatch branch :547-559.
+// The classes in the order the reference decides them: s_qlen < 0 exits; then the SV branches (:475-546) by dis alone; then the mismatch
+// class, which exits on s_tlen < 0 (ksw_extend_core, ksw.c:672) and on a window outside the contig.
+enum { JC_SV, JC_MIS, JC_DEL, JC_EXIT };       // SV branches (split_sv) | mismatch class with read bases between the seeds (a DP job) | without (tl reference bases deleted) | the reference exits
+struct JGeo {
+    int s1, s2, at1_ld, at1_chr, at2_chr, did, s_qlen, dis, match_dis, cls;
+    int qoff; int32_t tl;            // the read bases between the seeds start at cur_read + qoff (get_read_intv, :116); JC_MIS / JC_DEL: window length, clipped
+    int64_t at1_off, at2_off, start0;       // start0: 0-based window start of the mismatch class
+};
+HP_INL void junction_geo(const ReadCtx &r, const FLines &F, int f1, int f2, JGeo &G)
+{
+    const lamsa_hp_para *P = r.cx.P;
+    const int32_t *sd1 = F.fr_seed + F.fr_seed_off[f1], *sd2 = F.fr_seed + F.fr_seed_off[f2];
+    const int n1 = F.fr_seed_off[f1 + 1] - F.fr_seed_off[f1], n2 = F.fr_seed_off[f2 + 1] - F.fr_seed_off[f2];
+    const bool plus = r.h_strand[sd1[0]] == 1;
+    if (plus) { G.s1 = sd1[0]; G.s2 = sd2[n2 - 1]; } else { G.s1 = sd1[n1 - 1]; G.s2 = sd2[0]; }
+    G.at1_off = r.h_pos[G.s1]; G.at1_ld = r.h_len_dif[G.s1]; G.at1_chr = r.h_chr[G.s1];
+    G.at2_off = r.h_pos[G.s2]; G.at2_chr = r.h_chr[G.s2];
+    const int id1 = sid(r, r.n_seed[G.s1]);
+    G.did = sid(r, r.n_seed[G.s2]) - id1;
+    G.s_qlen = G.did * P->seed_step - P->seed_len;
+    G.qoff = (plus ? 0 : r.last_len) + id1 * P->seed_step - P->seed_inv;
+    const int64_t exp = G.at1_off + G.at1_ld + (int64_t)(G.did * P->seed_step);
+    G.dis = (int)(G.at2_off - exp);
+    G.match_dis = P->match_dis * ((P->aln_mode & 2) ? G.did : 1);
+    G.tl = 0; G.start0 = 0;
+    if (G.s_qlen < 0) { G.cls = JC_EXIT; return; }
+    if (G.dis > G.match_dis || G.dis < -G.match_dis) { G.cls = JC_SV; return; }
+    G.tl = G.s_qlen + G.dis;
+    G.start0 = G.at1_off + P->seed_len + G.at1_ld - 1;
+    if (G.tl < 0 || !contig_clip(r.ref, G.at1_chr, G.start0, G.tl)) { G.cls = JC_EXIT; return; }
+    G.cls = G.s_qlen > 0 ? JC_MIS : JC_DEL;
+}
+
+// Gap between seed `last` and the seed s walked after it in a fragment (frag_extend :360-385; plus: the fragment's strand): the read interval
+// (get_read_intv, :116) and the reference window (get_ref_intv, :98), clipped.  false: the reference exits.
+struct GapGeo { int qoff, qlen, chr; int64_t start0; int32_t tlen; };
+HP_INL bool gap_geo(const ReadCtx &r, bool plus, int last, int s, GapGeo &G)
+{
+    const lamsa_hp_para *P = r.cx.P;
+    const int base = plus ? 0 : r.last_len;
+    const int e = base + (sid(r, r.n_seed[s]) - 1) * P->seed_step;
+    G.qoff = base + sid(r, r.n_seed[last]) * P->seed_step - P->seed_inv;
+    G.qlen = e > G.qoff ? e - G.qoff : 0;
+    G.chr = r.h_chr[last];
+    G.start0 = r.h_pos[last] + P->seed_len - 1 + r.h_len_dif[last];
+    G.tlen = (int32_t)(r.h_pos[s] - 1 - G.start0);
+    if (G.tlen <= 0) { G.tlen = 0; return true; }                  // no reference base between them: nothing is fetched
+    return contig_clip(r.ref, G.chr, G.start0, G.tlen);
+}
+
+// The bounds of a line as frag_check uses them: those of a '-' line are flipped (:926-930).  F keeps them as chaining left them.
+HP_INL void line_bounds(const ReadCtx &r, const FLines &F, int line, int strand, int &lb, int &rb)
+{
+    lb = strand == 1 ? F.left_bound[line] : r.seed_all + 1 - F.right_bound[line];
+    rb = strand == 1 ? F.right_bound[line] : r.seed_all + 1 - F.left_bound[line];
+}
+
+// End extension of a line: frag_head_bound_fix :576-654 (head) / frag_tail_bound_fix :656-707.  r.flip must be set for the line's strand.
+// The head extends from the seed that comes first on the strand-appropriate read (the last seed of a '+' line, the first of a '-' line)
+// towards the read's start, the tail from the other end seed towards its end.  EG_NONE: nothing to extend (G.s is still set: the head's
+// record then begins at h_pos[G.s]); EG_EXIT: the reference exits (read_len < 0, or a window outside the contig); EG_JOB: an extension over
+// read_len >= 0 read bases and ref_len reference bases, clipped.
+enum { EG_NONE, EG_JOB, EG_EXIT };
+struct EndGeo { int s, read_start, read_len, chr; int64_t start0; int32_t ref_len; };
+HP_INL int end_geo(const ReadCtx &r, const FLines &F, int line, int strand, bool head, EndGeo &G)
+{
+    const lamsa_hp_para *P = r.cx.P;
+    const bool plus = strand == 1;
+    const int f0 = F.frag_off[line], f1 = F.frag_off[line + 1];
+    int lb, rb; line_bounds(r, F, line, strand, lb, rb);
+    G.s = head == plus ? F.fr_seed[F.fr_seed_off[f1] - 1] : F.fr_seed[F.fr_seed_off[f0]];
+    const int id = sid(r, r.n_seed[G.s]), base = plus ? 0 : r.last_len;
+    int64_t ref_start;
+    if (head) {                                                                  // :592-640
+        if (plus && id == 1) return EG_NONE;
+        G.read_len = (lb == 0 ? base : P->seed_inv) + (id - 1 - lb) * P->seed_step;
+        G.read_start = lb == 0 ? 0 : base + lb * P->seed_step - P->seed_inv;
+        if (!plus && G.read_len == 0) return EG_NONE;
+    } else {                                                                     // :670-699
+        if (!plus && id == r.seed_all) return EG_NONE;
+        G.read_len = (rb == r.seed_all + 1 ? r.last_len - base : P->seed_inv) + (rb - 1 - id) * P->seed_step;
+        G.read_start = base + id * P->seed_step - P->seed_inv;
+        if (plus && G.read_len == 0) return EG_NONE;
+    }
+    if (G.read_len < 0) return EG_EXIT;
+    G.ref_len = G.read_len + P->hash_step * 2;
+    if (head) {
+        ref_start = r.h_pos[G.s] - G.ref_len;
+        if (ref_start < 1) { ref_start = 1; G.ref_len = (int32_t)(r.h_pos[G.s] - 1); }
+    } else ref_start = r.h_pos[G.s] + P->seed_len + r.h_len_dif[G.s];
+    G.chr = r.h_chr[G.s];
+    G.start0 = ref_start - 1;
+    return contig_clip(r.ref, G.chr, G.start0, G.ref_len) ? EG_JOB : EG_EXIT;
+}
+
 // ---------------------------------------------------------------- pac2fa_core, bntseq.c:465-477
 HP_FN bool ref_fetch(ReadCtx &r, int chr, int64_t start0, int32_t *len, uint8_t *dst)
 {
     HP_T0(tr0_);
-    const int32_t clen = r.ref.seq_len[chr - 1];
-    if (start0 > clen || start0 < 0) { r.cx.status |= ST_REFEXIT; return false; }      // exit(1), :469-472
-    if (start0 + *len > clen) *len = (int32_t)(clen - start0);                          // :474
+    if (!contig_clip(r.ref, chr, start0, *len)) { r.cx.status |= ST_REFEXIT; return false; }      // exit(1), :469-472
     const int64_t k0 = r.ref.seq_off[chr - 1] + start0;
     const int32_t n = *len;
     r.t_bases += n > 0 ? n : 0;
@@ -245,55 +356,40 @@ HP_INL bool merge_cigar(ReadCtx &r, CigV &c1, int64_t *c1_refend, int *c1_readen
     return true;
 }
 
-// read interval between two chained seeds (get_read_intv, :116): pointer into the strand-appropriate read
-HP_INL int read_gap(const ReadCtx &r, int s1, int s2, const uint8_t **p)
-{
-    const lamsa_hp_para *P = r.cx.P;
-    int i, e;
-    if (r.h_strand[s1] == 1) { i = sid(r, r.n_seed[s1]) * P->seed_step - P->seed_inv; e = (sid(r, r.n_seed[s2]) - 1) * P->seed_step; }
-    else { i = r.last_len + sid(r, r.n_seed[s1]) * P->seed_step - P->seed_inv; e = r.last_len + (sid(r, r.n_seed[s2]) - 1) * P->seed_step; }
-    *p = r.cur_read + i;
-    return e > i ? e - i : 0;
-}
-
 // ---------------------------------------------------------------- frag_extend, :332-410
 #ifndef HP_FRAG_BLOCK_MIN
 #define HP_FRAG_BLOCK_MIN 3                  // fewer steps than this are walked one by one (the tests' CPU build sets it to 1 and to a large number)
 #endif
 HP_INL int seed_at_after_block(const HP_G int32_t *g_seed, int i, int step, int nb) { return g_seed[i + step * (nb - 1)]; }
 
-// One seed step of the loop :360-400, as the reference runs it: the gap between seed `last` and seed s (its CIGAR computed ahead by the lane-DP
+// One seed step of the loop :360-400, as the reference runs it: the gap between seed `last` and seed s (its CIGAR computed ahead by a DP
 // launch, or ksw_global2 here), then seed s's own CIGAR, each through merge_cigar.
 HP_INL bool frag_step(ReadCtx &r, const FLines &F, int frag, int i, int chr, CigV &fc, int64_t &ref_end, int &re, int &last)
 {
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
-    const int32_t *seed = F.fr_seed + F.fr_seed_off[frag];
-    const int s = seed[i];
-    {   const int32_t *gt = F.gt ? F.gt + 4 * (F.fr_seed_off[frag] + i) : nullptr;
-        if (gt && gt[3] && F.jarena) {                                          // the gap's CIGAR was computed ahead (hp_lanedp.h)
-            const uint8_t *qp0; const int len1p = read_gap(r, last, s, &qp0);
-            const bool ok = merge_cigar(r, fc, &ref_end, &re, chr, F.jarena + gt[0], gt[1], gt[2], len1p) &&
-                            (r.cs_words += r.h_cig_n[s], merge_cigar(r, fc, &ref_end, &re, chr, r.cig + r.h_cig_off[s], r.h_cig_n[s], P->seed_len + r.h_len_dif[s], P->seed_len));
-            last = s;
-            return ok;
-        }
-    }
+    const int s = F.fr_seed[F.fr_seed_off[frag] + i];
+    GapGeo g;
+    const bool inside = gap_geo(r, r.h_strand[last] == 1, last, s, g);
+    const int32_t *gt = F.gt ? F.gt + GS_WORDS * (F.fr_seed_off[frag] + i) : nullptr;
     const size_t m2 = arena_mark(cx.tmp);
-    // get_ref_intv, :98
-    const int64_t start = r.h_pos[last] + P->seed_len - 1 + r.h_len_dif[last];
-    int32_t len2 = (int32_t)(r.h_pos[s] - 1 - start);
-    uint8_t *tb = nullptr;
-    if (len2 <= 0) len2 = 0;
+    const cig_t *gc; int gn; int32_t len2;                                     // the gap's CIGAR and the reference bases it covers
+    if (gt && gt[GS_HAS] && F.jarena) { gc = F.jarena + gt[GS_OFF]; gn = gt[GS_N]; len2 = gt[GS_TLEN]; }       // computed ahead
     else {
-        tb = (uint8_t *)arena_alloc(cx, (size_t)len2 + 16);
-        if (!tb || !ref_fetch(r, r.h_chr[last], start, &len2, tb)) return false;
+        if (!inside) { cx.status |= ST_REFEXIT; return false; }
+        uint8_t *tb = nullptr;
+        len2 = g.tlen;
+        if (len2 > 0) {
+            tb = (uint8_t *)arena_alloc(cx, (size_t)len2 + 16);
+            if (!tb || !ref_fetch(r, g.chr, g.start0, &len2, tb)) return false;
+        }
+        const uint8_t *qp = r.cur_read + g.qoff;
+        CigV c;
+        if (!cig_alloc(cx, c, g.qlen + len2 + 8)) return false;
+        ksw_global(cx, g.qlen, seq_fwd(qp), len2, seq_fwd(tb ? tb : qp), P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, P->band_w, &c);
+        gc = c.c; gn = c.n;
     }
-    const uint8_t *qp; const int len1 = read_gap(r, last, s, &qp);
-    CigV g;
-    if (!cig_alloc(cx, g, len1 + len2 + 8)) return false;
-    ksw_global(cx, len1, seq_fwd(qp), len2, seq_fwd(tb ? tb : qp), P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, P->band_w, &g);
-    const bool ok = merge_cigar(r, fc, &ref_end, &re, chr, g.c, g.n, len2, len1) &&
+    const bool ok = merge_cigar(r, fc, &ref_end, &re, chr, gc, gn, len2, g.qlen) &&
                     (r.cs_words += r.h_cig_n[s], merge_cigar(r, fc, &ref_end, &re, chr, r.cig + r.h_cig_off[s], r.h_cig_n[s], P->seed_len + r.h_len_dif[s], P->seed_len));
     last = s;
     arena_release(cx.tmp, m2);
@@ -315,11 +411,11 @@ HP_INL int frag_steps_block(ReadCtx &r, const FLines &F, int frag, int i, int st
     if (!F.gt || !F.jarena || fc.n < 1 || (top & 0xf) != C_M) return 0;
     const int fro = F.fr_seed_off[frag];
     const HP_G int32_t *g_seed = (const HP_G int32_t *)(F.fr_seed + fro);
-    const HP_G int32_t *g_gt = (const HP_G int32_t *)(F.gt + 4 * (size_t)fro);
+    const HP_G int32_t *g_gt = (const HP_G int32_t *)(F.gt + GS_WORDS * (size_t)fro);
     const HP_G cig_t *g_ja = (const HP_G cig_t *)F.jarena, *g_cig = (const HP_G cig_t *)r.cig;
     const int nb = n_steps < 32 ? n_steps : 32, K = 2 * nb;
-    const int seed_len = P->seed_len, seed_step = P->seed_step, seed_inv = P->seed_inv;
-    const int plus = r.h_strand[last] == 1, base_off = plus ? 0 : r.last_len;
+    const int seed_len = P->seed_len;
+    const bool plus = r.h_strand[last] == 1;
     wv::Lane<int> n, wf, wl, rl, ql, cw; wv::Lane<long long> src;
     WAVE_FOR(l) {
         n[l] = 0; wf[l] = 0; wl[l] = 0; rl[l] = 0; ql[l] = 0; cw[l] = 0; src[l] = 0;
@@ -327,10 +423,10 @@ HP_INL int frag_steps_block(ReadCtx &r, const FLines &F, int frag, int i, int st
             const int j = l >> 1, idx = i + step * j;
             const int s = g_seed[idx], prev = j == 0 ? last : g_seed[idx - step];
             if (!(l & 1)) {                                                     // the gap in front of seed s
-                int g[4]; hp_load16(g_gt + 4 * (size_t)idx, g);
-                if (g[3]) {
-                    const int a = base_off + sid(r, r.n_seed[prev]) * seed_step - seed_inv, e = base_off + (sid(r, r.n_seed[s]) - 1) * seed_step;      // read_gap
-                    n[l] = g[1]; src[l] = (long long)(g_ja + g[0]); rl[l] = g[2]; ql[l] = e > a ? e - a : 0;
+                int g[GS_WORDS]; hp_load16(g_gt + GS_WORDS * (size_t)idx, g);
+                if (g[GS_HAS]) {
+                    GapGeo gg; gap_geo(r, plus, prev, s, gg);                   // (for the read bases it covers)
+                    n[l] = g[GS_N]; src[l] = (long long)(g_ja + g[GS_OFF]); rl[l] = g[GS_TLEN]; ql[l] = gg.qlen;
                 } else n[l] = -1;                                               // not computed ahead
             } else {                                                            // seed s itself
                 n[l] = r.h_cig_n[s]; src[l] = (long long)(g_cig + r.h_cig_off[s]); rl[l] = seed_len + r.h_len_dif[s]; ql[l] = seed_len; cw[l] = n[l];
@@ -435,21 +531,15 @@ HP_INL bool frag_extend(ReadCtx &r, const FLines &F, int frag, Rec &res)
     return ok && !(r.cx.status & (ST_REFEXIT | ST_OVERFLOW));
 }
 
-// ---------------------------------------------------------------- split_mapping, :416-564
-// Geometry of the junction between two fragments (:424-470), computed once and handed to whichever branch applies.
-struct SplitGeo {
-    const uint8_t *qp; int64_t at1_off, at2_off; int at1_ld, at1_chr, at2_chr, did, s_qlen, dis, match_dis;
-    const int32_t *jt; const int32_t *jarena;        // this junction's slot of FLines::jt (or nullptr) and the arena its offset refers to
-};
-
+// ---------------------------------------------------------------- split_mapping, :416-564 (its geometry: junction_geo)
 // DEL / INS / DUP branches (:475-546): the structural-variant cases, rare on ordinary reads
-HP_NOINL bool split_sv(ReadCtx &r, const SplitGeo &g, Rec &res)
+HP_NOINL bool split_sv(ReadCtx &r, const JGeo &g, Rec &res)
 {
     HP_STAT(28);
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
     const int hash_len = P->hash_len, s_qlen = g.s_qlen, dis = g.dis;
-    const uint8_t *qp = g.qp;
+    const uint8_t *qp = r.cur_read + g.qoff;
     const int64_t at1_off = g.at1_off, at2_off = g.at2_off;
     const int at1_ld = g.at1_ld, at1_chr = g.at1_chr, at2_chr = g.at2_chr;
     const int gh0 = hash_len * P->match;
@@ -505,26 +595,22 @@ HP_NOINL bool split_sv(ReadCtx &r, const SplitGeo &g, Rec &res)
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
 }
 
-// mismatch class with read bases between the seeds (:547-559): two-sided extension
-HP_NOINL bool split_mismatch(ReadCtx &r, const SplitGeo &g, Rec &res)
+// mismatch class with read bases between the seeds (:547-559): two-sided extension; jt: the junction's slot of FLines::jt (or nullptr)
+HP_NOINL bool split_mismatch(ReadCtx &r, const JGeo &g, const int32_t *jt, const int32_t *jarena, Rec &res)
 {
     HP_STAT(29);
     Ctx &cx = r.cx;
-    const lamsa_hp_para *P = cx.P;
-    int s_tlen = g.s_qlen + g.dis;
-    if (s_tlen < 0) { cx.status |= ST_REFEXIT; return false; }                 // ksw_extend_core exit(-1), ksw.c:672
-    if (g.jt && g.jt[3] && g.jarena) {                                          // its CIGAR was computed ahead (hp_lanedp.h)
-        return merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, g.jarena + g.jt[0], g.jt[1], g.jt[2], g.s_qlen) && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
+    if (jt && jt[GS_HAS] && jarena) {                                           // its CIGAR was computed ahead
+        return merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, jarena + jt[GS_OFF], jt[GS_N], jt[GS_TLEN], g.s_qlen) && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
     }
     const size_t mark = arena_mark(cx.tmp);
-    int32_t tl = s_tlen;
+    int32_t tl = g.tl;
     CigV sc;
-    uint8_t *tb = (uint8_t *)arena_alloc(cx, (size_t)s_tlen + 16);
-    bool ok = tb && cig_alloc(cx, sc, g.s_qlen + s_tlen + 64) && ref_fetch(r, g.at1_chr, g.at1_off + P->seed_len + g.at1_ld - 1, &tl, tb);
+    uint8_t *tb = (uint8_t *)arena_alloc(cx, (size_t)tl + 16);
+    bool ok = tb && cig_alloc(cx, sc, g.s_qlen + tl + 64) && ref_fetch(r, g.at1_chr, g.start0, &tl, tb);
     if (ok) {
-        s_tlen = tl;
-        ksw_bi_extend(cx, g.s_qlen, seq_fwd(g.qp), s_tlen, seq_fwd(tb), 100, 100, sc);
-        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, sc.c, sc.n, s_tlen, g.s_qlen);
+        ksw_bi_extend(cx, g.s_qlen, seq_fwd(r.cur_read + g.qoff), tl, seq_fwd(tb), 100, 100, sc);
+        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, sc.c, sc.n, tl, g.s_qlen);
     }
     arena_release(cx.tmp, mark);
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
@@ -533,45 +619,21 @@ HP_NOINL bool split_mismatch(ReadCtx &r, const SplitGeo &g, Rec &res)
 HP_INL bool split_mapping(ReadCtx &r, const FLines &F, int f1, int f2, Rec &res)
 {
     Ctx &cx = r.cx;
-    const lamsa_hp_para *P = cx.P;
-    const int32_t *sd1 = F.fr_seed + F.fr_seed_off[f1], *sd2 = F.fr_seed + F.fr_seed_off[f2];
-    const int n1 = F.fr_seed_off[f1 + 1] - F.fr_seed_off[f1], n2 = F.fr_seed_off[f2 + 1] - F.fr_seed_off[f2];
-    int s1, s2;
-    if (r.h_strand[sd1[0]] == 1) { s1 = sd1[0]; s2 = sd2[n2 - 1]; }
-    else { s1 = sd1[n1 - 1]; s2 = sd2[0]; }
-    SplitGeo g;
-    g.at1_off = r.h_pos[s1]; g.at2_off = r.h_pos[s2];
-    g.at1_ld = r.h_len_dif[s1]; g.at1_chr = r.h_chr[s1]; g.at2_chr = r.h_chr[s2];
-    g.did = sid(r, r.n_seed[s2]) - sid(r, r.n_seed[s1]);
-    g.s_qlen = g.did * P->seed_step - P->seed_len;
-    if (g.s_qlen < 0) { cx.status |= ST_REFEXIT; return false; }
-    read_gap(r, s1, s2, &g.qp);
-    const int64_t exp = g.at1_off + g.at1_ld + (int64_t)(g.did * P->seed_step);
-    g.dis = (int)(g.at2_off - exp);
-    g.match_dis = P->match_dis * ((P->aln_mode & 2) ? g.did : 1);
-    g.jt = F.jt ? F.jt + 4 * (f1 < f2 ? f1 : f2) : nullptr; g.jarena = F.jarena;
-    if (g.dis > g.match_dis || g.dis < -g.match_dis) return split_sv(r, g, res);
-    if (g.s_qlen > 0) return split_mismatch(r, g, res);
+    JGeo g; junction_geo(r, F, f1, f2, g);
+    if (g.cls == JC_EXIT) { cx.status |= ST_REFEXIT; return false; }
+    if (g.cls == JC_SV) return split_sv(r, g, res);
+    if (g.cls == JC_MIS) return split_mismatch(r, g, F.jt ? F.jt + GS_WORDS * (f1 < f2 ? f1 : f2) : nullptr, F.jarena, res);
     // Mismatch class with no read base between the seeds (neighbouring seeds overlap by design, so this is most
     // junctions of a noisy read): ksw_bi_extend has nothing to align and returns "delete the whole target"
-    // (see the shortcut in ksw_bi_extend).  The reference still cuts the window at the contig end (bntseq.c:469-474),
-    // which is reproduced here; the window itself is not needed.
-    int s_tlen = g.dis;
-    if (s_tlen < 0) { cx.status |= ST_REFEXIT; return false; }                 // ksw_extend_core exit(-1), ksw.c:672
-    {
-        const int64_t start0 = g.at1_off + P->seed_len + g.at1_ld - 1;
-        const int32_t clen = r.ref.seq_len[g.at1_chr - 1];
-        if (start0 > clen || start0 < 0) { cx.status |= ST_REFEXIT; return false; }
-        if (start0 + s_tlen > clen) s_tlen = (int)(clen - start0);
-    }
-    if (s_tlen <= 0) return !(cx.status & (ST_REFEXIT | ST_OVERFLOW));          // empty CIGAR: merge_cigar returns at once (:254)
+    // (see the shortcut in ksw_bi_extend); the window itself is not needed, only its clipped length.
+    if (g.tl <= 0) return !(cx.status & (ST_REFEXIT | ST_OVERFLOW));            // empty CIGAR: merge_cigar returns at once (:254)
     const size_t mark = arena_mark(cx.tmp);
     cig_t *w = (cig_t *)arena_alloc(cx, sizeof(cig_t));
     bool ok = w != nullptr;
     if (ok) {
-        ((HP_G cig_t *)w)[0] = (s_tlen << 4) | C_D;
+        ((HP_G cig_t *)w)[0] = (g.tl << 4) | C_D;
         wv::sync();
-        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, w, 1, s_tlen, 0);
+        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, g.at1_chr, w, 1, g.tl, 0);
     }
     arena_release(cx.tmp, mark);
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
@@ -587,29 +649,6 @@ HP_INL bool split_mapping(ReadCtx &r, const FLines &F, int f1, int f2, Rec &res)
 // step per lane (the dependent loads of 64 steps overlap), and the sequential part keeps the last element of the growing CIGAR in
 // a register: appending is then a store, never a load.  Everything else (fragments of several seeds, SV junctions, DPs that were
 // not computed ahead, the boundary repair of merge_cigar) goes through the general routines above.
-struct JGeo { int s1, s2, at1_ld, at1_chr, did, s_qlen, dis, match_dis, cls, tl; int64_t at1_off, start0; };   // cls 0: general routine, 1: mismatch class with read bases, 2: without
-HP_INL void junction_geo(const ReadCtx &r, const FLines &F, int f1, int f2, JGeo &G)
-{   // split_mapping :424-470 and the window of its mismatch branch (:547-559, pac2fa_core bntseq.c:469-474)
-    const lamsa_hp_para *P = r.cx.P;
-    const int32_t *sd1 = F.fr_seed + F.fr_seed_off[f1], *sd2 = F.fr_seed + F.fr_seed_off[f2];
-    const int n1 = F.fr_seed_off[f1 + 1] - F.fr_seed_off[f1], n2 = F.fr_seed_off[f2 + 1] - F.fr_seed_off[f2];
-    if (r.h_strand[sd1[0]] == 1) { G.s1 = sd1[0]; G.s2 = sd2[n2 - 1]; } else { G.s1 = sd1[n1 - 1]; G.s2 = sd2[0]; }
-    G.at1_off = r.h_pos[G.s1]; G.at1_ld = r.h_len_dif[G.s1]; G.at1_chr = r.h_chr[G.s1];
-    G.did = sid(r, r.n_seed[G.s2]) - sid(r, r.n_seed[G.s1]);
-    G.s_qlen = G.did * P->seed_step - P->seed_len;
-    const int64_t exp = G.at1_off + G.at1_ld + (int64_t)(G.did * P->seed_step);
-    G.dis = (int)(r.h_pos[G.s2] - exp);
-    G.match_dis = P->match_dis * ((P->aln_mode & 2) ? G.did : 1);
-    G.cls = 0; G.tl = 0; G.start0 = 0;
-    if (G.s_qlen < 0 || G.dis > G.match_dis || G.dis < -G.match_dis || G.s_qlen + G.dis < 0) return;
-    G.start0 = G.at1_off + P->seed_len + G.at1_ld - 1;
-    const int32_t clen = r.ref.seq_len[G.at1_chr - 1];
-    if (G.start0 > clen || G.start0 < 0) return;
-    G.tl = G.s_qlen + G.dis;
-    if (G.start0 + G.tl > clen) G.tl = (int)(clen - G.start0);
-    G.cls = G.s_qlen > 0 ? 1 : 2;
-}
-
 // p == nullptr: a one-element CIGAR, the element in `first`; ls: the CIGAR's words staged in the wave's LDS (or nullptr -- NOT tested: `staged` says)
 struct MergeSrc { const cig_t *p; int n, first, last, reflen, readlen; const HP_L int32_t *ls; bool staged; };
 // Short CIGARs of a 64-step block of frags_merge are staged in the wave's LDS when the block's plan is made (all of them requested at once, one
@@ -721,15 +760,16 @@ HP_NOINL bool frags_merge(ReadCtx &r, const FLines &F, int f0, int nfr, int stra
                     const int f2 = strand == 1 ? f - 1 : f + 1;
                     JGeo G; junction_geo(r, F, f, f2, G);
                     v[8] = 3; v[15] = G.at1_chr;                                   // 3: the general routine
-                    if (G.cls == 2) { v[8] = G.tl > 0 ? 1 : 0; v[10] = 1; v[11] = v[12] = (G.tl << 4) | C_D; v[13] = G.tl; v[14] = 0; }       // 1: deletion of the bases between the seeds, 0: nothing
-                    else if (G.cls == 1) {
-                        const int32_t *jt = F.jt ? F.jt + 4 * (f < f2 ? f : f2) : nullptr;
-                        if (jt && jt[3] && F.jarena) {                                  // 2: computed ahead
-                            v[8] = 2; v[9] = jt[0]; v[10] = jt[1]; v[13] = jt[2]; v[14] = G.s_qlen; if (jt[1] > 0) { v[11] = F.jarena[jt[0]]; v[12] = F.jarena[jt[0] + jt[1] - 1]; }
-                            if (stage && jt[1] > 0 && jt[1] <= FM_JW) {
+                    if (G.cls == JC_DEL) { v[8] = G.tl > 0 ? 1 : 0; v[10] = 1; v[11] = v[12] = (G.tl << 4) | C_D; v[13] = G.tl; v[14] = 0; }       // 1: deletion of the bases between the seeds, 0: nothing
+                    else if (G.cls == JC_MIS) {
+                        const int32_t *jt = F.jt ? F.jt + GS_WORDS * (f < f2 ? f : f2) : nullptr;
+                        if (jt && jt[GS_HAS] && F.jarena) {                             // 2: computed ahead
+                            v[8] = 2; v[9] = jt[GS_OFF]; v[10] = jt[GS_N]; v[13] = jt[GS_TLEN]; v[14] = G.s_qlen;
+                            if (jt[GS_N] > 0) { v[11] = F.jarena[jt[GS_OFF]]; v[12] = F.jarena[jt[GS_OFF] + jt[GS_N] - 1]; }
+                            if (stage && jt[GS_N] > 0 && jt[GS_N] <= FM_JW) {
                                 int w[FM_JW];
 #pragma unroll
-                                for (int k = 0; k < FM_JW; ++k) w[k] = k < jt[1] ? (int)F.jarena[jt[0] + k] : 0;
+                                for (int k = 0; k < FM_JW; ++k) w[k] = k < jt[GS_N] ? (int)F.jarena[jt[GS_OFF] + k] : 0;
 #pragma unroll
                                 for (int k = 0; k < FM_JW; ++k) stg[l * FM_W + FM_SW + k] = w[k];
                             }
@@ -812,50 +852,36 @@ HP_NOINL bool frags_merge(ReadCtx &r, const FLines &F, int f0, int nfr, int stra
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
 }
 
-// ---------------------------------------------------------------- frag_head_bound_fix, :576-654
+// ---------------------------------------------------------------- frag_head_bound_fix, :576-654 (its geometry: end_geo)
 HP_NOINL bool head_fix(ReadCtx &r, const FLines &F, int line, Rec &res)
 {
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
-    const int left_bound = F.left_bound[line];
-    const int f0 = F.frag_off[line], fl = F.frag_off[line + 1] - 1;
-    int s, read_len, read_start;
-    if (r.h_strand[F.fr_seed[F.fr_seed_off[f0]]] == 1) {
-        s = F.fr_seed[F.fr_seed_off[fl + 1] - 1];                       // last seed of the last fragment
-        if (sid(r, r.n_seed[s]) != 1) {
-            read_len = (left_bound == 0 ? 0 : P->seed_inv) + (sid(r, r.n_seed[s]) - left_bound - 1) * P->seed_step;
-            if (read_len < 0) { cx.status |= ST_REFEXIT; return false; }
-            read_start = left_bound == 0 ? 0 : left_bound * P->seed_step - P->seed_inv;
-        } else { res.offset = r.h_pos[s]; res.refend = res.offset - 1; res.cig.n = 0; return true; }
-    } else {
-        s = F.fr_seed[F.fr_seed_off[f0]];
-        read_len = (left_bound == 0 ? r.last_len : P->seed_inv) + (sid(r, r.n_seed[s]) - 1 - left_bound) * P->seed_step;
-        if (read_len == 0) { res.offset = r.h_pos[s]; res.refend = res.offset - 1; res.cig.n = 0; return true; }
-        if (read_len < 0) { cx.status |= ST_REFEXIT; return false; }
-        read_start = left_bound == 0 ? 0 : r.last_len + left_bound * P->seed_step - P->seed_inv;
-    }
-    res.offset = r.h_pos[s];
-    {   const int32_t *ht = F.ht ? F.ht + 16 * line : nullptr;
-        if (ht && ht[4] && F.jarena) {                                      // the extension was computed ahead (hp_wavejob.h): its CIGAR, clipped and turned round
+    EndGeo g;
+    const int kind = end_geo(r, F, line, r.h_strand[F.fr_seed[F.fr_seed_off[F.frag_off[line]]]], true, g);
+    if (kind == EG_EXIT) { cx.status |= ST_REFEXIT; return false; }
+    res.offset = r.h_pos[g.s];
+    if (kind == EG_NONE) { res.refend = res.offset - 1; res.cig.n = 0; return true; }
+    {   const int32_t *ht = F.ht ? F.ht + ES_LINE * line : nullptr;
+        if (ht && ht[ES_HAS] && F.jarena) {                                 // the extension was computed ahead (hp_wavejob.h): its CIGAR, clipped and turned round
             HP_STAT(20);
-            res.offset -= ht[2];
+            res.offset -= ht[ES_REFLEN];
             res.refend = res.offset - 1;
-            cig_pushv(cx, res.cig, F.jarena + ht[0], ht[1]);                // _push_cigar_e, frag_check.h:193
-            res.refend += ht[2];
-            res.readend += ht[3];
+            cig_pushv(cx, res.cig, F.jarena + ht[ES_OFF], ht[ES_N]);        // _push_cigar_e, frag_check.h:193
+            res.refend += ht[ES_REFLEN];
+            res.readend += ht[ES_READLEN];
             return !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
         }
     }
-    int32_t ref_len = read_len + P->hash_step * 2;
-    int64_t ref_start = r.h_pos[s] - ref_len;
-    if (ref_start < 1) { ref_start = 1; ref_len = (int32_t)(r.h_pos[s] - 1); }
+    const int read_len = g.read_len;
+    int32_t ref_len = g.ref_len;
     const size_t mark = arena_mark(cx.tmp);
     uint8_t *tb = (uint8_t *)arena_alloc(cx, (size_t)(ref_len > 0 ? ref_len : 0) + 16);
     CigV c;
-    bool ok = tb && cig_alloc(cx, c, read_len + ref_len + 16) && ref_fetch(r, r.h_chr[s], ref_start - 1, &ref_len, tb);
+    bool ok = tb && cig_alloc(cx, c, read_len + ref_len + 16) && ref_fetch(r, g.chr, g.start0, &ref_len, tb);
     if (ok) {
         int qre, tre;
-        const int rr = ksw_extend_r(cx, read_len, seq_fwd(r.cur_read + read_start), ref_len, seq_fwd(tb), P->band_w, P->seed_len * P->match, &qre, &tre, &c);
+        const int rr = ksw_extend_r(cx, read_len, seq_fwd(r.cur_read + g.read_start), ref_len, seq_fwd(tb), P->band_w, P->seed_len * P->match, &qre, &tre, &c);
         if (rr != 0) cig_push1(cx, c, ((read_len - qre) << 4) | C_S);
         cig_invert(c.c, c.n);
         res.offset -= cig_reflen(c.c, c.n);
@@ -868,44 +894,32 @@ HP_NOINL bool head_fix(ReadCtx &r, const FLines &F, int line, Rec &res)
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
 }
 
-// ---------------------------------------------------------------- frag_tail_bound_fix, :656-707
+// ---------------------------------------------------------------- frag_tail_bound_fix, :656-707 (its geometry: end_geo)
 HP_NOINL bool tail_fix(ReadCtx &r, const FLines &F, int line, Rec &res)
 {
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
-    const int right_bound = F.right_bound[line];
-    const int f0 = F.frag_off[line], fl = F.frag_off[line + 1] - 1;
-    int s, read_len, read_start;
-    if (r.h_strand[F.fr_seed[F.fr_seed_off[f0]]] == 1) {
-        s = F.fr_seed[F.fr_seed_off[f0]];
-        read_start = sid(r, r.n_seed[s]) * P->seed_step - P->seed_inv;
-        read_len = (right_bound == r.seed_all + 1 ? r.last_len : P->seed_inv) + (right_bound - 1 - sid(r, r.n_seed[s])) * P->seed_step;
-        if (read_len == 0) return true;
-        if (read_len < 0) { cx.status |= ST_REFEXIT; return false; }
-    } else {
-        s = F.fr_seed[F.fr_seed_off[fl + 1] - 1];
-        if (sid(r, r.n_seed[s]) == r.seed_all) return true;
-        read_start = sid(r, r.n_seed[s]) * P->seed_step - P->seed_inv + r.last_len;
-        read_len = (right_bound == r.seed_all + 1 ? 0 : P->seed_inv) + (right_bound - 1 - sid(r, r.n_seed[s])) * P->seed_step;
-        if (read_len < 0) { cx.status |= ST_REFEXIT; return false; }
-    }
-    {   const int32_t *ht = F.ht ? F.ht + 16 * line + 8 : nullptr;
-        if (ht && ht[4] && F.jarena) {                                      // computed ahead (hp_wavejob.h), clipped
+    EndGeo g;
+    const int kind = end_geo(r, F, line, r.h_strand[F.fr_seed[F.fr_seed_off[F.frag_off[line]]]], false, g);
+    if (kind == EG_EXIT) { cx.status |= ST_REFEXIT; return false; }
+    if (kind == EG_NONE) return true;
+    {   const int32_t *ht = F.ht ? F.ht + ES_LINE * line + ES_WORDS : nullptr;
+        if (ht && ht[ES_HAS] && F.jarena) {                                 // computed ahead (hp_wavejob.h), clipped
             HP_STAT(21);
-            return merge_cigar(r, res.cig, &res.refend, &res.readend, r.h_chr[s], F.jarena + ht[0], ht[1], ht[2], ht[3]) && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
+            return merge_cigar(r, res.cig, &res.refend, &res.readend, g.chr, F.jarena + ht[ES_OFF], ht[ES_N], ht[ES_REFLEN], ht[ES_READLEN]) && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
         }
     }
-    int32_t ref_len = read_len + P->hash_step * 2;
-    const int64_t ref_start = r.h_pos[s] + P->seed_len + r.h_len_dif[s];
+    const int read_len = g.read_len;
+    int32_t ref_len = g.ref_len;
     const size_t mark = arena_mark(cx.tmp);
     uint8_t *tb = (uint8_t *)arena_alloc(cx, (size_t)ref_len + 16);
     CigV c;
-    bool ok = tb && cig_alloc(cx, c, read_len + ref_len + 16) && ref_fetch(r, r.h_chr[s], ref_start - 1, &ref_len, tb);
+    bool ok = tb && cig_alloc(cx, c, read_len + ref_len + 16) && ref_fetch(r, g.chr, g.start0, &ref_len, tb);
     if (ok) {
         int qle, tle;
-        const int rr = ksw_extend_c(cx, read_len, seq_fwd(r.cur_read + read_start), ref_len, seq_fwd(tb), P->band_w, P->seed_len * P->match, &qle, &tle, &c);
+        const int rr = ksw_extend_c(cx, read_len, seq_fwd(r.cur_read + g.read_start), ref_len, seq_fwd(tb), P->band_w, P->seed_len * P->match, &qle, &tle, &c);
         if (rr != 0) cig_push1(cx, c, ((read_len - qle) << 4) | C_S);
-        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, r.h_chr[s], c.c, c.n, cig_reflen(c.c, c.n), cig_readlen(c.c, c.n));
+        ok = merge_cigar(r, res.cig, &res.refend, &res.readend, g.chr, c.c, c.n, cig_reflen(c.c, c.n), cig_readlen(c.c, c.n));
     }
     arena_release(cx.tmp, mark);
     return ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW));
@@ -1141,7 +1155,7 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
 #else
 #define HP_TIMED(slot, call) (call)
 #endif
-HP_NOINL bool fill_line(ReadCtx &r, FLines &F, int line, LineRes &la, cig_t *cur_buf, int cur_cap, cig_t *rec_buf, int rec_cap)
+HP_NOINL bool fill_line(ReadCtx &r, const FLines &F, int line, LineRes &la, cig_t *cur_buf, int cur_cap, cig_t *rec_buf, int rec_cap)
 {
     Ctx &cx = r.cx;
     const lamsa_hp_para *P = cx.P;
@@ -1152,26 +1166,23 @@ HP_NOINL bool fill_line(ReadCtx &r, FLines &F, int line, LineRes &la, cig_t *cur
     Rec &r0 = la.rec[0];
     cig_bind(r0.cig, cur_buf, cur_cap);
     r0.nstrand = strand == 1 ? 1 : 0; r0.chr = r.h_chr[first_seed]; r0.readend = 0; r0.refend = 0; r0.offset = 0;
-    bool ok = true;
-    if (strand == 1) {
-        r.cur_read = r.read; r.flip = false;
-        if (F.left_bound[line] > 0) { const cig_t w = ((F.left_bound[line] * P->seed_step - P->seed_inv) << 4) | C_S; cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4); }
-        ok = HP_TIMED(32, head_fix(r, F, line, r0));
-        ok = ok && HP_TIMED(34, frags_merge(r, F, f0, nfr, strand, r0)) && HP_TIMED(38, tail_fix(r, F, line, r0));
-        if (ok && F.right_bound[line] <= r.seed_all) { const cig_t w = ((r.L - (F.right_bound[line] - 1) * P->seed_step) << 4) | C_S; cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4); }
-    } else {
+    if (strand == 1) { r.cur_read = r.read; r.flip = false; }
+    else {
         if (!r.rc_ready) {                                            // :922-925 (buffer reserved when the read was set up)
             for (int b = 0; b < r.L; b += 64) { WAVE_FOR(l) { const int i = b + l; if (i < r.L) { const int c = r.read[r.L - 1 - i]; r.rc_read[i] = c < 4 ? 3 - c : 4; } } }
             wv::sync();
             r.rc_ready = true;
         }
         r.cur_read = r.rc_read; r.flip = true;                        // :926
-        const int tmp = F.left_bound[line];
-        F.left_bound[line] = r.seed_all + 1 - F.right_bound[line]; F.right_bound[line] = r.seed_all + 1 - tmp;
-        if (F.left_bound[line] > 0) { const cig_t w = ((F.left_bound[line] * P->seed_step - P->seed_inv + r.last_len) << 4) | C_S; cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4); }
-        ok = HP_TIMED(32, head_fix(r, F, line, r0));
-        ok = ok && HP_TIMED(34, frags_merge(r, F, f0, nfr, strand, r0)) && HP_TIMED(38, tail_fix(r, F, line, r0));
-        if (ok && F.right_bound[line] <= r.seed_all) { const cig_t w = (((r.seed_all - F.right_bound[line] + 1) * P->seed_step - P->seed_inv) << 4) | C_S; cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4); }
+    }
+    int lb, rb; line_bounds(r, F, line, strand, lb, rb);              // (F itself is not written: the lister reads the same bounds)
+    // the read bases outside the line's bounds are soft-clipped in front of the head extension and behind the tail extension
+    if (lb > 0) { const cig_t w = ((lb * P->seed_step - P->seed_inv + (strand == 1 ? 0 : r.last_len)) << 4) | C_S; cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4); }
+    bool ok = HP_TIMED(32, head_fix(r, F, line, r0));
+    ok = ok && HP_TIMED(34, frags_merge(r, F, f0, nfr, strand, r0)) && HP_TIMED(38, tail_fix(r, F, line, r0));
+    if (ok && rb <= r.seed_all) {
+        const cig_t w = ((strand == 1 ? r.L - (rb - 1) * P->seed_step : (r.seed_all - rb + 1) * P->seed_step - P->seed_inv) << 4) | C_S;
+        cig_push1(cx, r0.cig, w); r0.readend += (int)(w >> 4);
     }
     ok = ok && HP_TIMED(40, res_split(r, la, rec_buf, rec_cap)) && HP_TIMED(42, res_aux(r, la));
     r.flip = false;                                                   // :953

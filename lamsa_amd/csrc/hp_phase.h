@@ -1,7 +1,7 @@
 // hp_phase.h -- the per-read path of hp_align.h cut at frag_dp_path into separate launches:
 //
 //   chain1  (one read per wave)   sort index, frag_line_BCC                       lamsa_dp_con.c:1305-1445
-//   list    (one LINE per wave)   the line's DP jobs into the queues of the batch (small ones for the lane-per-job launch, the others for the wave-per-job launch)
+//   list    (one LINE per wave)   the line's DP jobs, as the geometry routines of hp_fill.h describe them, into the queues of the batch (small ones for the lane-per-job launch, the others for the wave-per-job launch)
 //   dp      (64 jobs / one job per wave)   hp_lanedp.h / hp_wavejob.h: the CIGARs into the job arena
 //   fill    (one LINE per wave)   frag_check of one line of round 1 + its get_reg  frag_check.c:856-961, lamsa_aln.c:571-605
 //   chain2  (one read per wave)   get_remain_reg, frag_line_remain                lamsa_aln.c:550-569, lamsa_dp_con.c:1252-1302
@@ -252,7 +252,7 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
     Ctx &cx = r.cx;
     FillLoc *fl = (FillLoc *)arena_alloc(cx, sizeof(FillLoc));
     if (!fl) { meta_flag(a, rd, r); return; }                   // (a slab is never below 64 KiB: not reached)
-    FLines &F = fl->F;
+    FLines &F = fl->F;                                          // bound here, read-only from here on (fill_line takes it const)
     F.n = M.fl_n[round]; F.nfrag = M.fl_nfrag[round];
     flines_bind(F, a.fl_base + M.fl_off[round], F.n, M.fl_tot[round]);
     F.jarena = a.job_base;
@@ -315,12 +315,14 @@ HP_FN void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP_L 
 }
 
 // ---------------------------------------------------------------- fill, step 1: the DP jobs of the lines, computed ahead of the fill.
-// phase_filllist (one line per wave) lists the line's junctions of the mismatch class with read bases in between (split_mapping,
-// frag_check.c:547-559), the gaps between neighbouring seeds of its fragments (frag_extend, :360-400) and its two end extensions
-// (frag_head_bound_fix :576-654, frag_tail_bound_fix :656-707), with the geometry the fill would compute, into job queues of the whole batch:
-// jobs with queries of up to HP_LJ_QSMALL bases by kind and query length for phase_filldp (64 jobs per wave, one per LANE, hp_lanedp.h:
-// measured on the MI355X they are cheaper that way than one per wave, profiles/r02_*), everything else by cost for phase_wavejob (one job per
-// WAVE, hp_wavejob.h).  Both leave the CIGARs in the job arena and their slots in FLines::jt / gt / ht, where the fill finds them.
+// phase_filllist (one line per wave) lists the line's junctions of the mismatch class with read bases in between, the gaps between
+// neighbouring seeds of its fragments and its two end extensions into job queues of the whole batch: jobs with queries of up to HP_LJ_QSMALL
+// bases by kind and query length for phase_filldp (64 jobs per wave, one per LANE, hp_lanedp.h: measured on the MI355X they are cheaper that
+// way than one per wave, profiles/r02_*), everything else by cost for phase_wavejob (one job per WAVE, hp_wavejob.h).  Both leave the CIGARs
+// in the job arena and their slots in FLines::jt / gt / ht, where the fill finds them and merges them without looking at the sequences
+// again.  So a job must have exactly the read interval and the reference window the fill would use: both take them from junction_geo,
+// gap_geo and end_geo (the geometry section of hp_fill.h), and the lister holds no formula of its own.  It reads FLines and writes only
+// the queues; a job whose geometry makes the reference exit is not listed -- the fill meets it and flags it.
 struct LjRec { int64_t qaddr, tk, slot; int32_t rd; uint16_t tlen; uint8_t qlen; int8_t type_comp; };      // type_comp: type (1: ksw_bi_extend(100, 100), 2: ksw_global2) | complement << 4
 // queues of the lane jobs: kind 1 longest first, kind 2 longest first
 enum { LJ_NCLS = HP_LJ_QSMALL / 16, LJ_NBUCKET = 2 * LJ_NCLS };
@@ -328,59 +330,6 @@ HP_INL int lj_bucket_of(int type, int qlen)
 {
     const int cls = (qlen > 0 ? qlen - 1 : 0) >> 4;                            // 0 .. HP_LJ_QSMALL / 16 - 1
     return (type == 1 ? 0 : LJ_NCLS) + (LJ_NCLS - 1 - cls);
-}
-
-// end extension of line `line` as frag_head_bound_fix (head) / frag_tail_bound_fix computes it, with the line's bounds as the fill will see
-// them (a '-' line's are flipped, frag_check.c:926-930; r.flip must be set accordingly).  false: there is no DP to run ahead (no read base
-// to extend over, or a geometry the reference exits on, which is left to the fill to flag).
-struct EndGeo { int s, read_start, read_len, chr; int64_t start0; int32_t ref_len; };
-HP_INL bool end_geo(const ReadCtx &r, const FLines &F, int line, int strand, bool head, EndGeo &G)
-{
-    const lamsa_hp_para *P = r.cx.P;
-    const int f0 = F.frag_off[line], fl = F.frag_off[line + 1] - 1;
-    const int lb = strand == 1 ? F.left_bound[line] : r.seed_all + 1 - F.right_bound[line];
-    const int rb = strand == 1 ? F.right_bound[line] : r.seed_all + 1 - F.left_bound[line];
-    const int s_first = F.fr_seed[F.fr_seed_off[f0]], s_last = F.fr_seed[F.fr_seed_off[fl + 1] - 1];
-    int64_t ref_start;
-    if (head) {                                                                  // :592-640
-        if (strand == 1) {
-            G.s = s_last;
-            const int id = sid(r, r.n_seed[G.s]);
-            if (id == 1) return false;
-            G.read_len = (lb == 0 ? 0 : P->seed_inv) + (id - lb - 1) * P->seed_step;
-            G.read_start = lb == 0 ? 0 : lb * P->seed_step - P->seed_inv;
-        } else {
-            G.s = s_first;
-            G.read_len = (lb == 0 ? r.last_len : P->seed_inv) + (sid(r, r.n_seed[G.s]) - 1 - lb) * P->seed_step;
-            G.read_start = lb == 0 ? 0 : r.last_len + lb * P->seed_step - P->seed_inv;
-        }
-        if (G.read_len <= 0) return false;
-        G.ref_len = G.read_len + P->hash_step * 2;
-        ref_start = r.h_pos[G.s] - G.ref_len;
-        if (ref_start < 1) { ref_start = 1; G.ref_len = (int32_t)(r.h_pos[G.s] - 1); }
-    } else {                                                                     // :670-699
-        if (strand == 1) {
-            G.s = s_first;
-            const int id = sid(r, r.n_seed[G.s]);
-            G.read_start = id * P->seed_step - P->seed_inv;
-            G.read_len = (rb == r.seed_all + 1 ? r.last_len : P->seed_inv) + (rb - 1 - id) * P->seed_step;
-        } else {
-            G.s = s_last;
-            const int id = sid(r, r.n_seed[G.s]);
-            if (id == r.seed_all) return false;
-            G.read_start = id * P->seed_step - P->seed_inv + r.last_len;
-            G.read_len = (rb == r.seed_all + 1 ? 0 : P->seed_inv) + (rb - 1 - id) * P->seed_step;
-        }
-        if (G.read_len <= 0) return false;
-        G.ref_len = G.read_len + P->hash_step * 2;
-        ref_start = r.h_pos[G.s] + P->seed_len + r.h_len_dif[G.s];
-    }
-    G.chr = r.h_chr[G.s];
-    G.start0 = ref_start - 1;                                                    // pac2fa_core, bntseq.c:469-474
-    const int32_t clen = r.ref.seq_len[G.chr - 1];
-    if (G.start0 > clen || G.start0 < 0) return false;
-    if (G.start0 + G.ref_len > clen) G.ref_len = (int32_t)(clen - G.start0);
-    return G.ref_len > 0 && G.read_start >= 0 && G.read_start + G.read_len <= r.L;
 }
 
 HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot, HP_L int32_t *lds, ReadCtx &r)
@@ -401,7 +350,7 @@ HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot
     const int p0 = F.fr_seed_off[f0], np = F.fr_seed_off[f0 + nfr] - p0;       // the line's seeds in fr_seed
     const int strand = r.h_strand[F.fr_seed[p0]];
     const int n_junc = (nfr - 1) + np, n_cand = n_junc + 2;                    // junctions, seed gaps, then the head and the tail extension
-    r.flip = strand != 1;                                                      // seed ids as a '-' line sees them (frag_check.c:926)
+    r.flip = strand != 1;                                                      // seed ids as a '-' line sees them, like fill_line
     const int64_t rbase = a.in.read_off[rd];
     long long tb = 0;
     // the fragment of every seed of the line, written once fragment by fragment (a binary search per seed is eight dependent loads)
@@ -426,54 +375,25 @@ HP_NOINL void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot
         WAVE_FOR(l) {
             const int c = c0 + l;
             int type = 0, qoff = 0, qlen = 0, tlen = 0, rev = 0; long long k0 = 0, slot = 0;
-            if (c < nfr - 1) {                                                  // junction between fragments jf and jf + 1, split_mapping :416-470
+            if (c < nfr - 1) {                                                  // junction between fragments jf and jf + 1, in the order the fill walks them
                 const int jf = f0 + c;
-                const int f1 = strand == 1 ? jf + 1 : jf, f2 = strand == 1 ? jf : jf + 1;
-                const int32_t *sd1 = F.fr_seed + F.fr_seed_off[f1], *sd2 = F.fr_seed + F.fr_seed_off[f2];
-                const int n1 = F.fr_seed_off[f1 + 1] - F.fr_seed_off[f1], n2 = F.fr_seed_off[f2 + 1] - F.fr_seed_off[f2];
-                int s1, s2;
-                if (r.h_strand[sd1[0]] == 1) { s1 = sd1[0]; s2 = sd2[n2 - 1]; } else { s1 = sd1[n1 - 1]; s2 = sd2[0]; }
-                const int64_t at1_off = r.h_pos[s1], at2_off = r.h_pos[s2];
-                const int at1_ld = r.h_len_dif[s1], at1_chr = r.h_chr[s1];
-                const int id1 = sid(r, r.n_seed[s1]), did = sid(r, r.n_seed[s2]) - id1;
-                const int s_qlen = did * P->seed_step - P->seed_len;
-                const int64_t exp = at1_off + at1_ld + (int64_t)(did * P->seed_step);
-                const int dis = (int)(at2_off - exp);
-                const int match_dis = P->match_dis * ((P->aln_mode & 2) ? did : 1);
-                if (s_qlen > 0 && dis <= match_dis && dis >= -match_dis && s_qlen + dis >= 0) {
-                    const int64_t start0 = at1_off + P->seed_len + at1_ld - 1;
-                    const int32_t clen = r.ref.seq_len[at1_chr - 1];
-                    if (start0 <= clen && start0 >= 0) {                        // pac2fa_core, bntseq.c:469-474
-                        int tl_ = s_qlen + dis;
-                        if (start0 + tl_ > clen) tl_ = (int)(clen - start0);
-                        type = 1; qlen = s_qlen; tlen = tl_; slot = (F.jt + 4 * jf) - a.fl_base; k0 = r.ref.seq_off[at1_chr - 1] + start0;
-                        qoff = (strand == 1 ? 0 : r.last_len) + id1 * P->seed_step - P->seed_inv;      // get_read_intv, :116
-                    }
-                }
-            } else if (c < n_junc) {                                            // gap in front of the seed at position p, frag_extend :360-385
+                JGeo G; junction_geo(r, F, strand == 1 ? jf + 1 : jf, strand == 1 ? jf : jf + 1, G);
+                if (G.cls == JC_MIS) { type = 1; qoff = G.qoff; qlen = G.s_qlen; tlen = G.tl; slot = (F.jt + GS_WORDS * jf) - a.fl_base; k0 = r.ref.seq_off[G.at1_chr - 1] + G.start0; }
+            } else if (c < n_junc) {                                            // gap in front of the seed at position p of its fragment
                 const int p = p0 + (c - (nfr - 1));
-                const int lo = ((const HP_G int32_t *)frag_of)[p - p0];        // its fragment
-                const int fb = F.fr_seed_off[lo], fe = F.fr_seed_off[lo + 1], i = p - fb, seed_n = fe - fb;
-                const int ip = strand == 1 ? i + 1 : i - 1;                     // the seed walked before it
-                if (seed_n > 1 && ip >= 0 && ip < seed_n) {
-                    const int s = F.fr_seed[p], last = F.fr_seed[fb + ip];
-                    const int64_t start = r.h_pos[last] + P->seed_len - 1 + r.h_len_dif[last];
-                    int len2 = (int)(r.h_pos[s] - 1 - start);
-                    bool ok = true;
-                    const int32_t clen = r.ref.seq_len[r.h_chr[last] - 1];
-                    if (len2 <= 0) len2 = 0;
-                    else if (start > clen || start < 0) ok = false;
-                    else if (start + len2 > clen) len2 = (int)(clen - start);
-                    const int idl = sid(r, r.n_seed[last]), ids = sid(r, r.n_seed[s]);
-                    const int qi = (strand == 1 ? 0 : r.last_len) + idl * P->seed_step - P->seed_inv, qe = (strand == 1 ? 0 : r.last_len) + (ids - 1) * P->seed_step;
-                    const int len1 = qe > qi ? qe - qi : 0;
-                    if (ok) { type = 2; qlen = len1; tlen = len2; slot = (F.gt + 4 * p) - a.fl_base; qoff = qi; k0 = r.ref.seq_off[r.h_chr[last] - 1] + start; }
+                const int lo = ((const HP_G int32_t *)frag_of)[p - p0];
+                const int fb = F.fr_seed_off[lo], seed_n = F.fr_seed_off[lo + 1] - fb;
+                const int ip = p - fb + (strand == 1 ? 1 : -1);                 // the seed walked before it
+                GapGeo G;
+                if (seed_n > 1 && ip >= 0 && ip < seed_n && gap_geo(r, strand == 1, F.fr_seed[fb + ip], F.fr_seed[p], G)) {
+                    type = 2; qoff = G.qoff; qlen = G.qlen; tlen = G.tlen; slot = (F.gt + GS_WORDS * p) - a.fl_base; k0 = r.ref.seq_off[G.chr - 1] + G.start0;
                 }
-            } else if (c < n_cand && wave_ok) {                                 // the end extensions, frag_head_bound_fix :576 / frag_tail_bound_fix :656
+            } else if (c < n_cand && wave_ok) {                                 // the end extensions
                 const bool head = c == n_junc;
                 EndGeo G;
-                if (end_geo(r, F, line, strand, head, G)) {
-                    type = head ? 3 : 4; qlen = G.read_len; tlen = G.ref_len; slot = (F.ht + 16 * line + (head ? 0 : 8)) - a.fl_base;
+                // (an extension over no read base is the fill's: there is no DP to run ahead; the interval is checked against the read because the job reads it unguarded)
+                if (end_geo(r, F, line, strand, head, G) == EG_JOB && G.read_len > 0 && G.ref_len > 0 && G.read_start >= 0 && G.read_start + G.read_len <= r.L) {
+                    type = head ? 3 : 4; qlen = G.read_len; tlen = G.ref_len; slot = (F.ht + ES_LINE * line + (head ? 0 : ES_WORDS)) - a.fl_base;
                     // the head runs on both sequences reversed (ksw_extend_r, src/ksw.c:820): query base j = base read_len - 1 - j of the interval
                     qoff = head ? G.read_start + G.read_len - 1 : G.read_start; rev = head;
                     k0 = r.ref.seq_off[G.chr - 1] + G.start0 + (head ? G.ref_len - 1 : 0);
@@ -605,11 +525,15 @@ HP_FN void phase_filllist(const PhaseArgs &a, int round, int u, int wave_slot, H
     phase_filllist(a, round, u, wave_slot, lds, r);
 }
 
+// jobs in queue b of a round as the DP launches see it: the lister's counters move on past a full queue, the excess was never stored
+HP_INL int lj_queue_n(const PhaseArgs &a, int round, int b) { const int n = a.ctl->lj_bucket_n[round][b]; return n < a.lj_cap ? n : a.lj_cap; }
+HP_INL int wj_queue_n(const PhaseArgs &a, int round, int b) { const int n = a.ctl->wj_bucket_n[round][b]; return n < a.wj_cap ? n : a.wj_cap; }
+
 // group g of 64 jobs of the round's queues (the caller maps g to a queue and an offset)
 HP_INL void phase_filldp(const PhaseArgs &a, int round, int bucket, int off, int wave_slot, HP_L int32_t *lds, int qcap)
 {
     const lamsa_hp_para *P = &a.P;
-    const int n_in = a.ctl->lj_bucket_n[round][bucket] < a.lj_cap ? a.ctl->lj_bucket_n[round][bucket] : a.lj_cap;
+    const int n_in = lj_queue_n(a, round, bucket);
     const int cnt = n_in - off < 64 ? n_in - off : 64;
     char *slab = a.slab + (size_t)wave_slot * a.slab_fill;
     cig_t *cbuf = (cig_t *)slab;                                               // per lane three CIGAR buffers
@@ -648,7 +572,7 @@ HP_INL void phase_filldp(const PhaseArgs &a, int round, int bucket, int off, int
             int32_t *dst = a.job_base + base + pre[l];
             for (int k = 0; k < nw[l]; ++k) dst[k] = src[k];
             int32_t *slot = a.fl_base + (slotl[l] & 0xffffffffffffll);
-            slot[0] = (int32_t)(base + pre[l]); slot[1] = nw[l]; slot[2] = (int32_t)(slotl[l] >> 48); slot[3] = 1;
+            slot[GS_OFF] = (int32_t)(base + pre[l]); slot[GS_N] = nw[l]; slot[GS_TLEN] = (int32_t)(slotl[l] >> 48); slot[GS_HAS] = 1;
             if (cel[l] > 0) atomicAdd(&a.meta[rdl[l]].cells, cel[l]);
         }
     }
@@ -665,7 +589,7 @@ void phase_wavejob(const PhaseArgs &a, int round, int g, bool big, int wave_slot
 {
     const int b1 = big ? WJ_NBIG : WJ_NBUCKET;
     int b = big ? 0 : WJ_NBIG;
-    for (; b < b1 - 1; ++b) { const int nb = a.ctl->wj_bucket_n[round][b] < a.wj_cap ? a.ctl->wj_bucket_n[round][b] : a.wj_cap; if (g < nb) break; g -= nb; }
+    for (; b < b1 - 1; ++b) { const int nb = wj_queue_n(a, round, b); if (g < nb) break; g -= nb; }
     const int ji = wv::uni(a.wj_bucket[(size_t)b * a.wj_cap + g]);
     if (ji < 0) return;                                                        // (a slot of a reservation that did not fit)
     const WjRec R = a.wjobs[ji];
@@ -696,8 +620,8 @@ void phase_wavejob(const PhaseArgs &a, int round, int g, bool big, int wave_slot
         for (int b0 = 0; b0 < out.n; b0 += 64) { WAVE_FOR(l) { const int i = b0 + l; if (i < out.n) dst[i] = src[i]; } }
         HP_G int32_t *slot = (HP_G int32_t *)(a.fl_base + wv::uni64(R.slot));
         WAVE_FOR(l) {
-            if (type == WJ_BI || type == WJ_GLOBAL) { if (l < 4) slot[l] = l == 0 ? (int32_t)base : (l == 1 ? out.n : (l == 2 ? tlen : 1)); }
-            else if (l < 8) slot[l] = l == 0 ? (int32_t)base : (l == 1 ? out.n : (l == 2 ? o.reflen : (l == 3 ? o.readlen : (l == 4 ? 1 : 0))));
+            if (type == WJ_BI || type == WJ_GLOBAL) { if (l < GS_WORDS) slot[l] = l == GS_OFF ? (int32_t)base : (l == GS_N ? out.n : (l == GS_TLEN ? tlen : 1)); }
+            else if (l < ES_WORDS) slot[l] = l == ES_OFF ? (int32_t)base : (l == ES_N ? out.n : (l == ES_REFLEN ? o.reflen : (l == ES_READLEN ? o.readlen : (l == ES_HAS ? 1 : 0))));
         }
     }
     if (wv::leader()) atomicAdd(&a.ctl->wj_bytes, (unsigned long long)(qlen + (tlen + 3) / 4 + 4 * out.n + 32));

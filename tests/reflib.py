@@ -471,6 +471,23 @@ def emu_streams(batch, hp_para, scale=1, slab_bytes=256 << 20, phased=True, unit
     return split_streams(stream, off[:n], ln[:n]), st[:n].copy()
 
 
+def emu_streams_dplog(batch, hp_para, **kw):
+    """emu_streams with the CPU build's log of the two DP dispatchers on (HP_DPLOG in hp_ksw.h): the streams, the statuses and one row
+    (kind, qlen, tlen, band, cells) per DP call, in call order.  The lane routines of hp_lanedp.h do not log."""
+    E = emu()
+    E.emu_dplog.restype = C.c_longlong
+    E.emu_dplog.argtypes = [C.c_void_p, C.c_longlong]
+    E.emu_dplog_on(1)
+    try:
+        got, st = emu_streams(batch, hp_para, **kw)
+        cnt = E.emu_dplog(None, 0)
+        buf = np.zeros(max(cnt, 1), np.int64)
+        E.emu_dplog(buf.ctypes.data, cnt)
+    finally:
+        E.emu_dplog_on(0)
+    return got, st, buf[:cnt].reshape(-1, 5)
+
+
 def hp_batch_struct(batch, HpBatch):
     b = HpBatch()
     b.n_reads = batch.n_reads
