@@ -526,8 +526,13 @@ static void prof_report(Slot &T, const long long *d_prof, int n)
             std::vector<long long> pd((size_t)n * 64);
             hipMemcpy(pd.data(), d_prof + ((size_t)n + 1) * 64, sizeof(long long) * pd.size(), hipMemcpyDeviceToHost);
             long long sd[64] = {0}; for (int r = 0; r < n; ++r) for (int k = 0; k < 64; ++k) sd[k] += pd[(size_t)r * 64 + k];
-            const char *cn[] = {"one set, q <= 62", "packed, one set", "packed, two sets", "band 1 set", "band 2 sets", "band 4 sets", "int32 sets", "LDS / HBM rows"};
-            for (int c = 0; c < 8; ++c) fprintf(stderr, "[HP_PROF] wave jobs, ksw_extend %-18s %8lld Mcyc %10lld Mcells %9lld calls %10lld rows\n", cn[c], sd[4 * c] / 1000000, sd[4 * c + 1] / 1000000, sd[4 * c + 2], sd[4 * c + 3]);
+            const char *cn[] = {"one set, q <= 62", "packed, one set", "packed, two sets", "band 1 set slides", "band 2 sets slides", "band 4 sets slides", "int32 sets", "LDS / HBM rows",
+                                "band 1 set fixed", "band 2 sets fixed", "band 4 sets fixed"};
+            for (int c = 0; c < 11; ++c) fprintf(stderr, "[HP_PROF] wave jobs, ksw_extend %-18s %8lld Mcyc %10lld Mcells %9lld calls %10lld rows\n", cn[c], sd[4 * c] / 1000000, sd[4 * c + 1] / 1000000, sd[4 * c + 2], sd[4 * c + 3]);
+            // the junction jobs whose extension is "band 2 sets fixed", part by part
+            fprintf(stderr, "[HP_PROF] wave jobs, junctions of the class 'band 2 sets fixed': %lld jobs, wj_run %lld Mcyc of which staging %lld; ksw_bi_extend %lld Mcyc of which after the left extension %lld; "
+                            "in ksw_extend_band<2>: setup and first fill %lld, rows %lld, backtrack %lld Mcyc\n",
+                    sd[51], sd[50] / 1000000, sd[49] / 1000000, sd[47] / 1000000, sd[48] / 1000000, sd[44] / 1000000, sd[45] / 1000000, sd[46] / 1000000);
         }
         for (int q = 0; q < 8 && q < n; ++q) { int r = idx[q]; fprintf(stderr, "[HP_PROF] read %d L=%d:", r, T.h_len[r]); for (int k = 0; k < 11; ++k) fprintf(stderr, " %lld", pr[(size_t)r * 64 + k] / 1000000); fprintf(stderr, " | o_l %lld H %lld | targets %lld trips %lld init_Mcyc %lld\n", pr[(size_t)r * 64 + 14], pr[(size_t)r * 64 + 15], pr[(size_t)r * 64 + 11], pr[(size_t)r * 64 + 12], pr[(size_t)r * 64 + 13] / 1000000); }
     }

@@ -916,6 +916,15 @@ HP_NOINL ExtRes ksw_extend_regn(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
 #define HP_PK_RT 1                          // the tests' CPU build switches the packed routines off to reach the int32 register sets behind them
 #endif
 #define HP_PK_IDENT (-16000)
+// -DHP_PROF, wave-per-job launch: where a call of the class "two sets, the window holds the whole query" spends its cycles (Ctx::prof_dp slots 44 ..)
+#ifdef HP_PROF
+#define HP_PD2_T0(v) const long long v = wv::clock()
+#define HP_PD2_ADD(cx, on, slot, v) do { if ((cx).prof_dp && (on)) (cx).prof_dp[slot] += wv::clock() - (v); } while (0)
+#define HP_PD2_CLASS(qlen, w) (pkb_sets_q(qlen, w) == 2 && (qlen) + 3 <= 256)
+#else
+#define HP_PD2_T0(v) do { } while (0)
+#define HP_PD2_ADD(cx, on, slot, v) do { } while (0)
+#endif
 
 // ksw_extend_core for LONG queries -- the end extensions of a line, up to the whole read (frag_head_bound_fix / frag_tail_bound_fix,
 // src/frag_check.c:576-707) -- with the row's live WINDOW in registers, int16 pairs, 2 * NS consecutive columns per lane.
@@ -926,12 +935,16 @@ HP_NOINL ExtRes ksw_extend_regn(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
 // there (:692-694), i.e. what it reads from its full-length array when the band reaches a cell it never wrote.
 // What that buys over the LDS tiles (ksw_extend_lds: 64 columns per pass, ~90 instructions and eight LDS operations each, four passes
 // for a band of 201): everything a row does across lanes is done ONCE per row whatever NS -- the F scan (a lane scans its own columns,
-// then one exclusive prefix maximum over the lanes' totals, in two halves because the window wraps round the wave), the row maximum
+// then one exclusive prefix maximum over the lanes' totals, in two halves where the window may wrap round the wave), the row maximum
 // (one reduction of (H << 16 | column) keys: "last column among equals" is the larger key, :743-744), the one-column shift of H (inside
 // a lane but for one wave rotation), the first and last non-zero cell (:775-778: a ballot over the lanes, then two lanes' bit patterns).
 // Same recurrences, tie rules, band and z-drop logic as ksw_extend_reg; scores are bounded (pkb_extend_ok), the scan's keys use
-// columns relative to the row's first one.  The direction matrix is a nibble per cell in the wave's slab, a row = 64 * NS bytes indexed by
-// the slot, with the band limits of every row beside it.
+// columns relative to the row's first one (the sliding window) or to column 0 (the fixed one, below).  The direction matrix is a nibble per
+// cell in the wave's slab, a row = 64 * NS bytes indexed by the slot, with the band limits of every row beside it.
+// Two variants of the one body (round 9): most calls are junctions whose whole query fits the window (qlen + 3 <= 128 NS: 70 % of the
+// routine's wave cycles on 10-kbp ONT reads, profiles/r04_dp_routines.txt) and never use the circular window's machinery; FIXED compiles it out.
+// The row loop in the gfx950 ISA, all paths, VALU / scalar instructions: NS = 1 197 / 164 before, fixed 116 / 134, sliding 191 / 196; NS = 2
+// 339 / 255 before, fixed 199 / 139, sliding 329 / 250 (profiles/r09_extband_ab.txt -- static counts; that file says what has been timed).
 // sets for a query of qlen columns under band w: the window holds the band + 2 + the eight lanes being refilled + one lane of slack -- or the
 // whole query, and then never moves
 HP_INL int pkb_sets_q(int qlen, int w)
@@ -947,18 +960,43 @@ HP_INL bool pkb_extend_ok(const lamsa_hp_para *P, int qlen, int h0, int ns)
     return ns > 0 && mx > 0 && mx < 256 && pen >= 0 && pen < 4000 && P->ins_ext_e >= 0 && P->del_ext_e >= 0 && P->ins_ext_o >= 0 && P->del_ext_o >= 0 &&
            (long long)h0 + (long long)qlen * mx < 23000 && (long long)(128 * ns + 2) * ext < 8000 && qlen + 128 * ns < 32000;
 }
-template <int NS>
+// (H << 16 | column) of the two halves of a pair of cells: a byte shuffle of the two registers each (v_perm_b32)
+HP_INL int pkb_key_lo(int h, int j)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)__builtin_amdgcn_perm((unsigned)h, (unsigned)j, 0x05040100u);
+#else
+    return (int)(((unsigned)h << 16) | ((unsigned)j & 0xffffu));
+#endif
+}
+HP_INL int pkb_key_hi(int h, int j)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)__builtin_amdgcn_perm((unsigned)h, (unsigned)j, 0x07060302u);
+#else
+    return (int)(((unsigned)h & 0xffff0000u) | ((unsigned)j >> 16));
+#endif
+}
+// FIXED: the window holds the whole query (qlen + 3 <= 128 * NS), so column j stays in slot j from the first row to the last -- the lanes are in
+// column order as they are, and everything the circular window needs per row is compiled out: the refill test, the second scan over the lanes
+// that wrapped round, the rotation of lanes and ballots by the window's first lane, and the scan keys' column term, which is taken relative
+// to column 0 (j * e_ins < 8 000 by pkb_extend_ok, as (j - beg) * e_ins was) and is then a constant of the lane for the whole job.
+template <int NS, bool FIXED>
 HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w, int h0, CigV *out)
 {
     long long cells_ = 0;
     ExtRes er; er.score = 0; er.qle = 0; er.tle = 0;
     HP_T0(te0_);
     qlen = wv::uni(qlen); tlen = wv::uni(tlen); w = wv::uni(w); h0 = wv::uni(h0);
+    HP_PD2_T0(tp0_);
     const lamsa_hp_para *P = cx.P;
     const int o_ins = wv::uni(P->ins_ext_o), e_ins = wv::uni(P->ins_ext_e), o_del = wv::uni(P->del_ext_o), e_del = wv::uni(P->del_ext_e);
     const int end_bonus = wv::uni(P->end_bonus), zdrop = wv::uni(P->zdrop);
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     const int n_col = qlen < 2 * w + 1 ? qlen : 2 * w + 1;
+    // the scan keys' column term: j * e_ins, a constant of the lane, where the window is fixed -- but not with four sets, where holding four more
+    // registers through the row loop spills; there it stays (j - beg) * e_ins and is worked out again after the scan instead of held across it
+    constexpr bool KEY0 = FIXED && NS < 4, KEEP_JRE = NS < 4;
     constexpr int LC = 2 * NS, WN = 128 * NS, zs = 64 * NS;              // columns per lane, slots of the window, bytes of a row of the direction matrix
     const size_t mark = arena_mark(cx.tmp);
     uint8_t *z = (uint8_t *)arena_alloc(cx, (size_t)zs * tlen + 16);
@@ -988,13 +1026,22 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
             } \
             Hs[r_][l] = pk::pack(hv_[0], hv_[1]); Es[r_][l] = 0; qoh[r_][l] = oh_; qN[r_][l] = nn_; \
         } \
-        JB[l] = pk::rep(jb_); } while (0)
+        JB[l] = pk::pack(jb_, (jb_) + 1); } while (0)
     wv::Lane<int> Hs[NS], Es[NS], qoh[NS], qN[NS], hcur[NS], M[NS], INB[NS], JRE[NS], pre[NS], JB, tl;
     WAVE_FOR(l) { tl[l] = 4; HP_PKB_LOAD(LC * l); }
-    int top = WN;                                                          // columns [0, top) have been given their slots
+    if constexpr (FIXED) HP_STAT(16);
+    if constexpr (KEY0) {
+        WAVE_FOR(l) {
+#pragma unroll
+            for (int r = 0; r < NS; ++r) JRE[r][l] = pk::mul(pk::add(JB[l], pk::rep(2 * r)), EI);
+        }
+    }
+    int top = WN; (void)top;                                               // columns [0, top) have been given their slots
     int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1;
     int beg = 0, end = qlen;
     bool stop_rows = false;
+    HP_PD2_ADD(cx, NS == 2 && qlen + 3 <= WN, 44, tp0_);
+    HP_PD2_T0(tp1_);
     for (int ib = 0; ib < tlen && !stop_rows; ib += 64) {
         { WAVE_FOR(l) { const int ii = ib + l; tl[l] = ii < tlen ? gt[(long)ii * ts] : 4; } }
         const int ti_first = wv::bcast(tl, 0);
@@ -1014,50 +1061,56 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 if (beg == qlen) { max_ie = gscore > h1_init ? max_ie : i; gscore = gscore > h1_init ? gscore : h1_init; }       // :759-762 (the loop variable stands at beg)
                 stop_rows = true; break;
             }
-            if (end + 3 > top) {                                           // the band's right edge (next row's at most two further) nears the loaded columns: eight more lanes
+            if (!FIXED && end + 3 > top) {                                 // the band's right edge (next row's at most two further) nears the loaded columns: eight more lanes
                 const int lr = (top / LC) & 63;
                 WAVE_FOR(l) { const int d = (l - lr) & 63; if (d < 8) { const int jb = top + d * LC; HP_PKB_LOAD(jb); } }
                 top += 8 * LC;
             }
             const int tsh = ti & 3, tN = ti > 3 ? -1 : 0;                   // a target N scores -1 against everything
             const int BEG = pk::rep(beg), END = pk::rep(end), H1 = pk::rep(h1_init);
-            const int l0 = (beg / LC) & 63;                                // the lane of the window's first column: lanes l0 .. 63, then 0 .. l0 - 1, hold ascending columns
-            // ---- the lane's own columns: M, the scan keys max(M - oe_ins, 0) + (j - beg) * e_ins and their running maximum
+            const int l0 = FIXED ? 0 : (beg / LC) & 63;                    // the lane of the window's first column: lanes l0 .. 63, then 0 .. l0 - 1, hold ascending columns
+            const int F0 = KEY0 ? pk::rep(beg * e_ins) : 0;                // F(i,beg) = 0 carried along the row, in the keys' frame
+            // ---- the lane's own columns: M, the scan keys max(M - oe_ins, 0) + (j - beg) * e_ins (KEY0: j * e_ins) and their running maximum
             wv::Lane<int> ka, kb;
             WAVE_FOR(l) {
                 int run = HP_PK_IDENT;
 #pragma unroll
                 for (int r = 0; r < NS; ++r) {
-                    const int jp = pk::add(JB[l], pk::pack(2 * r, 2 * r + 1));
+                    const int jp = pk::add(JB[l], pk::rep(2 * r));
                     const int in = pk::neg_mask(pk::sub(jp, END)) & ~pk::neg_mask(pk::sub(jp, BEG));       // beg <= j < end, per half
                     const int eq = (qoh[r][l] >> tsh) & 0x00010001;
                     const int S = pk::add(pk::mul(eq, DSC), MIS) | qN[r][l] | tN;                          // HP_SUB(ti, qb)
                     const int hm = Hs[r][l];
                     const int m = pk::mul(pk::add(hm, S), pk::min_u(hm, 0x00010001));                      // hm ? hm + S : 0   (:737; hm is never negative)
                     const int t1 = pk::max(pk::sub(m, OEI), 0);
-                    const int jre = pk::mul(pk::sub(jp, BEG), EI);
+                    const int jre = KEY0 ? JRE[r][l] : pk::mul(pk::sub(jp, BEG), EI);
                     const int k = pk::sel(in, pk::add(t1, jre), IDENT);
                     const int klo = pk::lo(k), khi = pk::hi(k);
                     const int p0 = run; run = run > klo ? run : klo;
                     const int p1 = run; run = run > khi ? run : khi;
-                    M[r][l] = m; INB[r][l] = in; JRE[r][l] = jre; pre[r][l] = pk::pack(p0, p1);
+                    M[r][l] = m; INB[r][l] = in; if constexpr (!KEY0 && KEEP_JRE) JRE[r][l] = jre; pre[r][l] = pk::pack(p0, p1);
                 }
-                ka[l] = l >= l0 ? run : HP_PK_IDENT; kb[l] = l < l0 ? run : HP_PK_IDENT;
+                if constexpr (FIXED) { ka[l] = run; kb[l] = HP_PK_IDENT; }
+                else { ka[l] = l >= l0 ? run : HP_PK_IDENT; kb[l] = l < l0 ? run : HP_PK_IDENT; }
             }
-            // F along the row: the exclusive prefix maximum over the lanes before this one in column order
-            // (one scan while the window has not moved, the lanes then being in column order as they are, was measured: no gain)
-            const int topA = wv::scan_max_excl_top(ka, HP_PK_IDENT);
-            wv::scan_max_excl(kb, HP_PK_IDENT);
+            // F along the row: the exclusive prefix maximum over the lanes before this one in column order -- one scan when the window never
+            // moves, two when it may have wrapped round the wave.  (Round 4 tried the single scan behind a per-row test inside the one routine:
+            // no gain, the rest of the circular window's bookkeeping stayed.  As a routine of its own: profiles/r09_extband_ab.txt.)
+            int topA = HP_PK_IDENT;
+            if constexpr (FIXED) wv::scan_max_excl(ka, HP_PK_IDENT);
+            else { topA = wv::scan_max_excl_top(ka, HP_PK_IDENT); wv::scan_max_excl(kb, HP_PK_IDENT); }
             wv::Lane<int> best;
             WAVE_FOR(l) {
-                const int pl = l >= l0 ? ka[l] : (topA > kb[l] ? topA : kb[l]);
+                const int pl = FIXED ? ka[l] : (l >= l0 ? ka[l] : (topA > kb[l] ? topA : kb[l]));
                 const int PP = pk::rep(pl);
                 int zw = 0, bk = -1;
 #pragma unroll
                 for (int r = 0; r < NS; ++r) {
-                    const int jre = JRE[r][l], in = INB[r][l], m = M[r][l];
+                    const int jp = pk::add(JB[l], pk::rep(2 * r));
+                    const int jre = KEEP_JRE ? JRE[r][l] : pk::mul(pk::sub(jp, BEG), EI);
+                    const int in = INB[r][l], m = M[r][l];
                     const int pr = pk::max(pre[r][l], PP);
-                    int f = pk::max(pk::add(pk::sub(pr, jre), EI), pk::sub(0, jre));                        // F(i,beg) = 0 carried along the row
+                    int f = pk::max(pk::add(pk::sub(pr, jre), EI), pk::sub(F0, jre));                       // F(i,beg) = 0 carried along the row
                     const int tI = pk::max(pk::sub(m, OEI), 0);
                     int ee = Es[r][l];
                     const int m1 = pk::neg_mask(pk::sub(ee, m));                                           // M > E
@@ -1076,8 +1129,7 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                     hcur[r][l] = hc;
                     zw |= ((d | (d >> 12)) & 0xff) << (8 * r);
                     // row maximum, last column among equals (:743-744): the larger of (H << 16 | column); a column outside the band gives a negative key
-                    const int jp = pk::add(JB[l], pk::pack(2 * r, 2 * r + 1));
-                    const int k0 = (int)(((unsigned)hc << 16) | ((unsigned)jp & 0xffffu)), k1 = (int)(((unsigned)hc & 0xffff0000u) | ((unsigned)jp >> 16));
+                    const int k0 = pkb_key_lo(hc, jp), k1 = pkb_key_hi(hc, jp);
                     bk = bk > k0 ? bk : k0; bk = bk > k1 ? bk : k1;
                 }
                 best[l] = bk;
@@ -1087,14 +1139,6 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
             }
             int mrow = 0, mj = -1;
             { const int b = wv::reduce_max(best); if (b >= 0) { mrow = b >> 16; mj = b & 0xffff; } }
-            int h_last;                                                     // H(i, end - 1)
-            {
-                const int le = ((end - 1) / LC) & 63, sl = (end - 1) % LC;
-                int v = 0;
-#pragma unroll
-                for (int r = 0; r < NS; ++r) if ((sl >> 1) == r) v = wv::bcast(hcur[r], le);
-                h_last = (sl & 1) ? pk::hi(v) : pk::lo(v);
-            }
             // eh[j+1].h = H(i,j): the row one column up -- inside the lane, and the lane's first column from the lane below's last
             wv::Lane<int> rot = hcur[NS - 1], LB;
             wv::ror1(rot);
@@ -1116,7 +1160,12 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 }
                 LB[l] = bits;
             }
-            if (end == qlen) {                                             // :759-762
+            if (end == qlen) {                                             // :759-762, with H(i, end - 1) -- only these rows need it
+                const int le = FIXED ? (end - 1) / LC : ((end - 1) / LC) & 63, sl = (end - 1) % LC;
+                int v = 0;
+#pragma unroll
+                for (int r = 0; r < NS; ++r) if ((sl >> 1) == r) v = wv::bcast(hcur[r], le);
+                const int h_last = (sl & 1) ? pk::hi(v) : pk::lo(v);
                 max_ie = gscore > h_last ? max_ie : i;
                 gscore = gscore > h_last ? gscore : h_last;
             }
@@ -1133,8 +1182,8 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 if (any) {
                     const unsigned long long rt = l0 ? ((any >> l0) | (any << (64 - l0))) : any;          // bit d: the lane d lanes after l0
                     const int df = __builtin_ctzll(rt), dl = 63 - __builtin_clzll(rt);
-                    const int bf = wv::bcast(LB, (l0 + df) & 63), bl = wv::bcast(LB, (l0 + dl) & 63);
-                    const int bb = beg / LC;
+                    const int bf = wv::bcast(LB, FIXED ? df : (l0 + df) & 63), bl = wv::bcast(LB, FIXED ? dl : (l0 + dl) & 63);
+                    const int bb = FIXED ? 0 : beg / LC;                   // (FIXED: a lane's number is its place in column order)
                     const int jf = (bb + df) * LC + __builtin_ctz((unsigned)bf), jx = (bb + dl) * LC + (31 - __builtin_clz((unsigned)bl));
                     if (jf < end) nb = jf;
                     jl = jx;                                               // (index `end` alone: nb = end, jl = end)
@@ -1150,7 +1199,10 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
     if (gscore <= 0 || gscore <= max - end_bonus) { i = max_i; k = max_j; }   // :785-789
     else { i = max_ie; k = qlen - 1; }
     er.qle = k + 1; er.tle = i + 1; er.score = max;
+    HP_PD2_ADD(cx, NS == 2 && qlen + 3 <= WN, 45, tp1_);
+    HP_PD2_T0(tp2_);
     if (out) { wv::sync(); HP_T0(tb0_); dp_backtrack(cx, nullptr, z, rowb, n_col, w, i, k, *out, zs); HP_TADD(cx, 28, tb0_); }
+    HP_PD2_ADD(cx, NS == 2 && qlen + 3 <= WN, 46, tp2_);
     cx.n_cells += cells_;
     arena_release(cx.tmp, mark);
     HP_TADD(cx, 26, te0_);
@@ -1515,8 +1567,11 @@ HP_INL int ksw_extend(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w, int h0, 
         // for half the columns -- 5.8 k wave cycles against 4.8 k -- and is gone: profiles/r04_dp_routines.txt.)
         HP_STAT(22);
         const int ns = pkb_sets_q(qlen, w);
-        cls_ = ns == 1 ? 3 : (ns == 2 ? 4 : 5);
-        er = ns == 1 ? ksw_extend_band<1>(cx, qlen, q, tlen, t, w, h0, out) : (ns == 2 ? ksw_extend_band<2>(cx, qlen, q, tlen, t, w, h0, out) : ksw_extend_band<4>(cx, qlen, q, tlen, t, w, h0, out));
+        cls_ = (ns == 1 ? 3 : (ns == 2 ? 4 : 5)) + (qlen + 3 <= 128 * ns ? 5 : 0);      // 3 .. 5: the window slides, 8 .. 10: it holds the whole query
+        if (qlen + 3 <= 128 * ns)                                          // (pkb_sets_q's second clause) the window holds the whole query
+            er = ns == 1 ? ksw_extend_band<1, true>(cx, qlen, q, tlen, t, w, h0, out) : (ns == 2 ? ksw_extend_band<2, true>(cx, qlen, q, tlen, t, w, h0, out) : ksw_extend_band<4, true>(cx, qlen, q, tlen, t, w, h0, out));
+        else
+            er = ns == 1 ? ksw_extend_band<1, false>(cx, qlen, q, tlen, t, w, h0, out) : (ns == 2 ? ksw_extend_band<2, false>(cx, qlen, q, tlen, t, w, h0, out) : ksw_extend_band<4, false>(cx, qlen, q, tlen, t, w, h0, out));
     }
     else if (qlen <= HP_REGN_QMAX(2)) { HP_STAT(17); cls_ = 6; er = ksw_extend_regn<2>(cx, qlen, q, tlen, t, w, h0, out); }
     else if (qlen <= HP_REGN_QMAX(3) && HP_REGN_SETS >= 3) { HP_STAT(17); cls_ = 6; er = ksw_extend_regn<3>(cx, qlen, q, tlen, t, w, h0, out); }
@@ -1611,6 +1666,7 @@ HP_NOINL int ksw_bi_extend(Ctx &cx_, int qlen, Seq q, int tlen, Seq t, int lh0, 
         return 0;
     }
     HP_T0(tbi0_);
+    HP_PD2_T0(tpb0_);
     const size_t mark = arena_mark(cx.tmp);
     int ret = 0, res, lqe, lte, rqe, rte;
     CigV L, R;
@@ -1621,6 +1677,7 @@ HP_NOINL int ksw_bi_extend(Ctx &cx_, int qlen, Seq q, int tlen, Seq t, int lh0, 
     res = ksw_extend_c(cx, qlen, q, tlen, t, w, lh0, &lqe, &lte, &L);
     res = wv::uni(res); lqe = wv::uni(lqe); lte = wv::uni(lte);
     HP_T0(tbi1_);
+    HP_PD2_T0(tpb1_);
     if (res < 2) {                                                                          // :875-880
         cig_pushv(cx, out, L.c, L.n);
         cig_push1(cx, out, res == 0 ? ((tlen - lte) << 4) | C_D : ((qlen - lqe) << 4) | C_I);
@@ -1642,6 +1699,8 @@ HP_NOINL int ksw_bi_extend(Ctx &cx_, int qlen, Seq q, int tlen, Seq t, int lh0, 
         }
     }
     arena_release(cx.tmp, mark);
+    HP_PD2_ADD(cx, HP_PD2_CLASS(qlen, w), 47, tpb0_);                     // (the w of this call before ksw_extend's :696-704 narrows it: the class test is the caller's)
+    HP_PD2_ADD(cx, HP_PD2_CLASS(qlen, w), 48, tpb1_);
     HP_TADD(cx, 50, tbi1_);
     HP_TADD(cx, 48, tbi0_);
     return ret;

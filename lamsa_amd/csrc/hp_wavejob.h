@@ -6,7 +6,8 @@
 // frag_tail_bound_fix :656-707 -> ksw_extend_c, up to the whole read long).  None of them depends on the line's growing CIGAR -- only
 // merge_cigar (:251), which joins their results, is sequential -- so the listing launch (phase_filllist, hp_phase.h) writes them as job
 // records with the geometry the fill would compute, and this launch runs them one per wavefront, costliest first: a launch that is all
-// instruction issue (VALU port 100 % busy, profiles/r04_ont10k_pmc.json) before a fill launch that is all memory latency (wait 85 %), instead of one kernel that is both; the
+// instruction issue (VALU port 100 % busy, profiles/r04_ont10k_pmc.json; 87 lane-slots per cell update against ~22 for the recurrence -- round 9 cut the row loop of the
+// extensions whose window never moves by ~40 % of its instructions, profiles/r09_extband_ab.txt, not yet timed) before a fill launch that is all memory latency (wait 85 %), instead of one kernel that is both; the
 // direction matrix of the two-columns-per-lane routines lies in the wave's LDS where it fits (a junction of up to 80 rows).  The fill finds the
 // CIGARs in the job arena (FLines::jt / gt / ht) and goes on with merge_cigar; a job that was not listed, or whose buffers did not suffice, is
 // run by the fill as before.
@@ -66,6 +67,7 @@ HP_FN bool wj_run(Ctx &cx, const uint8_t *reads, const uint8_t *pac, int type, i
     const lamsa_hp_para *P = cx.P;
     o.score = 0; o.qle = 0; o.tle = 0; o.reflen = 0; o.readlen = 0;
     out.n = 0;
+    HP_PD2_T0(tpw0_);
     uint8_t *qb = (uint8_t *)arena_alloc(cx, (size_t)(qlen > 0 ? qlen : 0) + 16), *tb = (uint8_t *)arena_alloc(cx, (size_t)(tlen > 0 ? tlen : 0) + 16);
     if (!qb || !tb) return false;
     {
@@ -75,6 +77,12 @@ HP_FN bool wj_run(Ctx &cx, const uint8_t *reads, const uint8_t *pac, int type, i
         for (int b = 0; b < tlen; b += 64) { WAVE_FOR(l) { const int i = b + l; if (i < tlen) { const int64_t k = tk + (int64_t)i * ts; gt[i] = (uint8_t)(gp[k >> 2] >> ((~k & 3) << 1) & 3); } } }      // _get_pac, bntseq.c:242
         wv::sync();
     }
+#ifdef HP_PROF
+    const int wcls_ = iabs(qlen - tlen) + 3 > P->band_w ? iabs(qlen - tlen) + 3 : P->band_w;
+    const bool pcls_ = type == WJ_BI && HP_PD2_CLASS(qlen, wcls_);
+    if (cx.prof_dp && pcls_) cx.prof_dp[51] += 1;
+#endif
+    HP_PD2_ADD(cx, pcls_, 49, tpw0_);
     const Seq q = seq_fwd(qb), t = seq_fwd(tb);
     if (type == WJ_BI) o.score = ksw_bi_extend(cx, qlen, q, tlen, t, h0, h0, out);      // (the "gap exists" flag)
     else if (type == WJ_GLOBAL) o.score = ksw_global(cx, qlen, q, tlen, t, P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, w, &out);
@@ -87,6 +95,7 @@ HP_FN bool wj_run(Ctx &cx, const uint8_t *reads, const uint8_t *pac, int type, i
         if (type == WJ_HEAD) cig_invert(out.c, out.n);
     }
     wv::sync();
+    HP_PD2_ADD(cx, pcls_, 50, tpw0_);
     if (cx.status & (ST_REFEXIT | ST_OVERFLOW)) return false;
     o.reflen = cig_reflen(out.c, out.n); o.readlen = cig_readlen(out.c, out.n);
     return true;
