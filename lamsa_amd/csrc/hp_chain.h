@@ -1762,6 +1762,7 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
         else {
             const HP_G int32_t *g_cs = (const HP_G int32_t *)C.cs, *g_srt = (const HP_G int32_t *)r.srt;
             HP_G uint8_t *g_big = (HP_G uint8_t *)C.big;
+            HP_STAT_MAX(48, C.n_cl);
             for (int c0 = 0; c0 < C.n_cl; c0 += 63) {
                 wv::Lane<int> csl;
                 WAVE_FOR(l) { const int c = c0 + l; csl[l] = c <= C.n_cl ? g_cs[c] : H; }
@@ -1772,14 +1773,15 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
                 if (geo32 && HP_CL_CAP_RT(1 << 20) >= HP_CLL_MCAP) {                                   // clusters of two to six hits: one per lane
                     const EdgeK K = edge_consts(P);
                     wv::sync();
-                    WAVE_FOR(l) { const int n = csn[l] - csl[l]; if (l < cn && n >= 2 && n <= HP_CLL_MCAP) cluster_lane(r, K, C, r.cx.lds + l, csl[l], n, do_me); }
+                    WAVE_FOR(l) { const int n = csn[l] - csl[l]; if (l < cn && n >= 2 && n <= HP_CLL_MCAP) { HP_STAT_ADD(34, 1); HP_STAT_MAX(47, n); cluster_lane(r, K, C, r.cx.lds + l, csl[l], n, do_me); } }
                     wv::sync();
                 }
                 for (int q = 0; q < cn; ++q) {
                     const int lo = wv::bcast(csl, q), n = wv::bcast(csl, q + 1) - lo;
                     if (n < 2) continue;                                                          // a lone hit has no predecessor
                     if (geo32 && HP_CL_CAP_RT(1 << 20) >= HP_CLL_MCAP && n <= HP_CLL_MCAP) continue;   // done above
-                    if (n <= HP_CL_CAP_RT(r.cx.lds_words / 5) && dp_cluster_lds(r, C, lo, n, do_me)) continue;
+                    if (n <= HP_CL_CAP_RT(r.cx.lds_words / 5) && dp_cluster_lds(r, C, lo, n, do_me)) { HP_STAT_ADD(32, 1); HP_STAT_MAX(40, n); continue; }
+                    HP_STAT_ADD(33, 1); HP_STAT_MAX(41, n);
                     if (do_me) min_extend_clusters(r, C, lo, lo + n);                             // the cluster goes through HBM: so does its MIN extension
                     for (int i0 = 0; i0 < n; i0 += 64) { WAVE_FOR(l) { if (i0 + l < n) g_big[g_srt[lo + i0 + l]] = 1; } }
                     any_big = true;
@@ -1825,6 +1827,8 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
 #endif
     LSet &S = loc->S;
     const bool staged = lset_stage(r, L, l_i, S);                     // the per-line arrays in LDS from here on, when they fit
+    HP_STAT_ADD(staged ? 35 : 36, 1);
+    HP_STAT_MAX(44, l_i);
     LSet &LL = staged ? S : L;
     const int line_n = set_bound(r, LL, 0, l_i, &T);                  // :1435
     const bool okf = build_flines(r, LL, line_n, F, fs);

@@ -70,12 +70,29 @@ struct Ctx {
 #define HP_TADD(cx, slot, v) do { } while (0)
 #endif
 
-// path counters of the tests' CPU build (tests/emu/emu_api.cpp defines HP_STAT): which variant of a routine a test has really run
+// path counters of the tests' CPU build (tests/emu/emu_api.cpp defines HP_STAT, HP_STAT_ADD and HP_STAT_MAX): which variant of a routine a test
+// has really run (HP_STAT, HP_STAT_ADD: counts), and how large the thing was that took it (HP_STAT_MAX: the largest value seen).  Slots:
+//  0 lines by cluster, 1 lines by seed range, 2 gaps in lanes, 3 of them from START, 4 gaps through the wave-wide routine, 5 of them through memory (hp_gaps.h),
+//  6-8 lines in clusters of <= 6 / <= 16 / more hits, 9 wave jobs published (hp_phase.h), 10 an uncovered region at the read's end (hp_align.h),
+//  11-13 the F_INSERT classes and the MULTI re-update of the k-mer split mapper, 30 its calls (hp_split.h), 14 inter-lines, 15 dumped edge clusters (hp_chain.h),
+//  16-19, 22, 31 the DP routines of hp_ksw.h, 20-21 head / tail extensions taken from a wave job, 24-29 fragment merging (hp_fill.h), 23 wave jobs on a big slab (emulation),
+//  32 clusters chained out of LDS (dp_cluster_lds), 33 clusters sent through HBM, 34 clusters handled one per lane (cluster_lane), 35 / 36 line sets staged in LDS / left in
+//  HBM (lset_stage), 37 / 38 sorts in one LDS block / in several (hp_sort.h), 39 gaps of the scan by seed range handed to a lane (gap_lane);
+//  largest values: 40 cluster chained out of LDS, 41 cluster sent through HBM, 42 hits listed for a wave-wide gap, 43 survivors of a gap a lane took,
+//  44 lines handed to lset_stage, 45 / 46 gaps of a line scanned by seed range / by cluster, 47 cluster handled by a lane, 48 clusters of a read
 #ifndef HP_DPLOG
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { } while (0)      // tests' CPU build: one record per DP call (tools/dp_shapes.py)
 #endif
 #ifndef HP_STAT
 #define HP_STAT(i) do { } while (0)
+#endif
+// (HP_STAT keeps the expansion it has always had: an empty loop and an empty expression are not the same to the compiler's block layout, and
+// the device code must not depend on whether a counter is there.  The two forms with a value are empty expressions.)
+#ifndef HP_STAT_ADD
+#define HP_STAT_ADD(i, n) ((void)0)
+#endif
+#ifndef HP_STAT_MAX
+#define HP_STAT_MAX(i, v) ((void)0)
 #endif
 
 // returns nullptr (and flags overflow) when the slab is exhausted; callers must cope

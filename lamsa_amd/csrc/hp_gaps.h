@@ -256,7 +256,8 @@ HP_NOINL GapRest gaps_one_by_one(ReadCtx &r, int G, int32_t *gp, int GA, int32_t
 // wave-wide routine on the listed hits beyond that.  Gaps without a survivor -- nearly all of them at the read's true locus, where
 // frag_min_extend has already promoted the colinear hit of every repetitive seed -- cost nothing: their mini line is empty and the
 // forced update of their right anchor finds no candidate (what it would leave in the anchor's score / NM / node_n is never read
-// again: the anchor is TRACKED, no later pass initialises, updates or scans it).
+// again: the anchor is TRACKED, no later pass initialises, updates or scans it).  The one exception is the gap beyond the line's end node:
+// without a better end node it takes the head's NM off the line's NM, survivors or not (see below).
 // gp: the per-gap arrays of line_build.  Returns pool_n >= 0, -1 (status flagged) or -2: not applicable (the caller scans by seed range).
 #ifndef HP_GAPTAB_CAP_RT
 #define HP_GAPTAB_CAP_RT(cap) (cap)          // slots the LDS table holds; the tests' CPU build lowers it
@@ -264,9 +265,7 @@ HP_NOINL GapRest gaps_one_by_one(ReadCtx &r, int G, int32_t *gp, int GA, int32_t
 #ifndef HP_GAP_MCAP_RT
 #define HP_GAP_MCAP_RT(cap) (cap)            // survivors of a gap a lane takes; the tests' CPU build lowers it
 #endif
-// HP_STAT slots: 0 lines by cluster, 1 lines by seed range, 2 gaps in lanes, 3 of them from START, 4 gaps through the wave-wide routine, 5 of them through memory,
-// 6-8 lines in clusters of <= 6 / <= 16 / more hits, 9 wave jobs published (hp_phase.h), 10 an uncovered region at the read's end
-// (hp_align.h), 11-13 the F_INSERT classes and the MULTI re-update of the k-mer split mapper (hp_split.h), 14 inter-lines, 15 dumped edge clusters
+// (the HP_STAT slots of the tests' CPU build are listed in hp_core.h)
 // The +-MULTI hits of the large clusters a read's lines have visited so far (ascending hit order, as in C.csrt): the ~20 lines of the read's
 // true locus share one cluster of several hundred hits, of which a few dozen are left for the mini DPs -- the first line lists them, the
 // others scan the list.  (A hit that a line has taken since is TRACKED; every scan tests the flag it loads anyway.)
@@ -410,6 +409,10 @@ HP_HOT GapRest gaps_by_cluster(ReadCtx &r, const Clusters &C, int max_node, int 
     // ---- the mini DPs, one gap per lane
     int pool_n = 0, d_score = 0, d_NM = 0;
     bool any_wide = false;
+    // The gap beyond the end node (tail == 0: always gap 0, the highest slots, so its survivors are the last run) ends at its best node or at
+    // its head; the reference starts that search with NM 0 (max_NM, :1105), so a gap that ends at its head takes the head's NM off the line
+    // (*de_NM += max_NM - old_NM, :1149) -- also when it has no survivor at all and none of the routines below runs for it.
+    if (G > 0 && g_tail[0] == 0 && !(n_surv > 0 && g_sv[8 * (size_t)(n_surv - 1) + 6] == 0)) d_NM -= g_hnm[g_left[0]];
 #define GW(e, w) strip[((e) * 6 + (w)) * 64]
     for (int q0 = 0; q0 < n_runs; q0 += 64) {
         wv::Lane<int> nn, ds, dn, gl;
@@ -423,7 +426,7 @@ HP_HOT GapRest gaps_by_cluster(ReadCtx &r, const Clusters &C, int max_node, int 
                 if (m > HP_GAP_MCAP_RT(HP_GAP_MCAP)) { O.n = -1; o_lane[g] = 0; o_s0[g] = s0; o_m[g] = m; }
                 else {
                     HP_L int32_t *strip = cx.lds + l;
-                    HP_STAT(2);
+                    HP_STAT(2); HP_STAT_MAX(43, m);
                     for (int e = 0; e < m; ++e) {
                         int u[4], v[4];
                         hp_load16(g_sv + 8 * (size_t)(s0 + e), u); hp_load16(g_sv + 8 * (size_t)(s0 + e) + 4, v);
@@ -490,7 +493,7 @@ HP_HOT GapRest gaps_by_cluster(ReadCtx &r, const Clusters &C, int max_node, int 
                 MiniR mr; mr.n = -1; mr.d_score = 0; mr.d_NM = 0;
                 if (cnt <= 64) mr = mini_line_sets<1>(r, left, right, right_x, _line, 1, tail, cnt, s_id + s0);
                 else if (cnt <= 64 * HP_MS_MAX_SETS) mr = mini_line_sets<HP_MS_MAX_SETS>(r, left, right, right_x, _line, 1, tail, cnt, s_id + s0);
-                HP_STAT(4);
+                HP_STAT(4); HP_STAT_MAX(42, cnt);
                 if (mr.n < 0) { HP_STAT(5); mr = mini_line_mem(r, left, right, right_x, _line, 1, tail); }
                 const int n = mr.n, dsc = mr.d_score, dnm = mr.d_NM;
                 if (cx.status & ST_REFEXIT) { arena_release(cx.tmp, mark); R.pool_n = -1; return R; }
@@ -633,11 +636,11 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
     if (C) {
         const GapRest gr = gaps_by_cluster(r, *C, max_node, G, gp, GA, pool, pool_mf, _line, gc, cl_lo, cl_n);
         if (gr.pool_n == -1) { arena_release(cx.tmp, mark); return -1; }
-        if (gr.pool_n >= 0) { by_cluster = true; pool_n = gr.pool_n; d_score = gr.d_score; d_NM = gr.d_NM; HP_STAT(0); }
+        if (gr.pool_n >= 0) { by_cluster = true; pool_n = gr.pool_n; d_score = gr.d_score; d_NM = gr.d_NM; HP_STAT(0); HP_STAT_MAX(46, G); }
         HP_LSTAMP(18);
     }
     if (!by_cluster) {
-        HP_STAT(1);
+        HP_STAT(1); HP_STAT_MAX(45, G);
         // ---- the mini DPs: one gap per lane (hp_gaps.h); what a lane cannot take goes through mini_line afterwards
         // (a lane walks the hit range of its gap by itself, one dependent load after the other: that pays when many gaps share the wait,
         // not for the two or three gaps of a short line)
@@ -647,7 +650,7 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
             WAVE_FOR(l) {
                 const int g = g0 + l;
                 GapOut O; O.n = -1; O.d_score = 0; O.d_NM = 0; O.r_from = -1; O.r_score = 0; O.r_NM = 0; O.r_nn = 1; O.r_mf = 0;
-                if (g < G && g_left[g] >= 0 && use_lanes) gap_lane(r, K, cx.lds + l, g_left[g], g_right[g], g_lx[g], g_rx[g], g_tail[g], O);
+                if (g < G && g_left[g] >= 0 && use_lanes) { HP_STAT_ADD(39, 1); gap_lane(r, K, cx.lds + l, g_left[g], g_right[g], g_lx[g], g_rx[g], g_tail[g], O); }
                 nn[l] = g < G ? O.n : 0; ds[l] = O.n >= 0 ? O.d_score : 0; dn[l] = O.n >= 0 ? O.d_NM : 0;
                 if (g < G) {
                     o_n[g] = O.n; o_ds[g] = O.d_score; o_dn[g] = O.d_NM; o_rf[g] = O.r_from; o_rs[g] = O.r_score; o_rn[g] = O.r_NM; o_rnn[g] = O.r_nn; o_rmf[g] = O.r_mf; o_lane[g] = O.n >= 0;

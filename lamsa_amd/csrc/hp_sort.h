@@ -109,6 +109,7 @@ HP_INL bool sort_packed(MajorFn major, int major_bits, int H, HP_G int32_t *srt,
     if (!(major_bits + ib <= 64 && lds_n >= C)) return false;
     // every block: packed straight into LDS, sorted there
     const bool one = H <= C;
+    HP_STAT_ADD(one ? 37 : 38, 1);
     for (int b0 = 0; b0 < H; b0 += C) {
         const int Hb = H - b0 < C ? H - b0 : C;
         for (int i = 0; i < Hb; i += 4 * wv::W) WAVE_FOR(l) {

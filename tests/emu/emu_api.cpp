@@ -20,11 +20,35 @@ int g_emu_pk = 1;                      // tests: 0 = extensions of 63 .. 254 que
 std::vector<long long> g_emu_dplog;    // one record per DP call of the fill: kind (0 extension, 1 global), query, target, band, cells
 int g_emu_dplog_on = 0;
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { if (g_emu_dplog_on) { g_emu_dplog.push_back(kind); g_emu_dplog.push_back(qlen); g_emu_dplog.push_back(tlen); g_emu_dplog.push_back(w); g_emu_dplog.push_back(cells); } } while (0)
-long long g_emu_stat[32];              // path counters (HP_STAT slots of the device sources)
+long long g_emu_stat[64];              // path counters (HP_STAT / HP_STAT_MAX slots of the device sources, listed in hp_core.h)
 #define HP_STAT(i) (++g_emu_stat[i])
+#define HP_STAT_ADD(i, n) (g_emu_stat[i] += (n))
+#define HP_STAT_MAX(i, v) do { if ((long long)(v) > g_emu_stat[i]) g_emu_stat[i] = (long long)(v); } while (0)
 #include "hp_dp_batch.h"
 
 using namespace hp;
+
+// ---------------------------------------------------------------- LDS buffers with guard words
+// Every buffer that stands for a wave's LDS is followed by EMU_GUARD_WORDS words of a fixed pattern, placed directly behind the `lds_words`
+// the phase is told it owns, and looked at after every call: an off-by-one record at a capacity edge lands there instead of in whatever
+// the device keeps behind its LDS (the chaining and fill kernels keep the wave's read context there).
+enum { EMU_GUARD_WORDS = 64, EMU_CHAIN_LDS_MAX = 5120 };
+static const int32_t EMU_GUARD_PAT = 0x5ca1ab1e;
+static long long g_emu_guard_hits = 0;
+static int g_emu_lds_shrink = 0;       // tests of the guards: those of the two chaining phases start this many words INSIDE the LDS the phase is told it owns
+extern "C" long long emu_lds_guard_hits() { return g_emu_guard_hits; }       // phase calls that damaged their guard words since the last reset
+extern "C" void emu_lds_guard_reset() { g_emu_guard_hits = 0; }
+extern "C" void emu_set_lds_shrink(int words) { g_emu_lds_shrink = words > 0 ? words : 0; }
+template <class F> static void emu_guarded(int32_t *lds, int words, F f, int shrink = 0)
+{
+    int32_t *g = lds + (words - shrink > 0 ? words - shrink : 0);
+    for (int i = 0; i < EMU_GUARD_WORDS; ++i) g[i] = EMU_GUARD_PAT;
+    f();
+    int bad = 0;
+    for (int i = 0; i < EMU_GUARD_WORDS; ++i) bad |= g[i] != EMU_GUARD_PAT;
+    g_emu_guard_hits += bad;
+}
+#define EMU_LDS(name, words) static thread_local int32_t name[(words) + EMU_GUARD_WORDS]
 
 extern "C" int emu_dp_batch(const lamsa_hp_para *P, int n, const uint8_t *seq,
                             const int64_t *q_off, const int32_t *qlen, const int64_t *t_off, const int32_t *tlen,
@@ -38,8 +62,8 @@ extern "C" int emu_dp_batch(const lamsa_hp_para *P, int n, const uint8_t *seq,
     a.cig_cap_off = cig_cap_off; a.cig = cig;
     std::vector<char> slab(slab_bytes);
     a.slab = slab.data(); a.slab_per_wave = slab_bytes; a.counter = nullptr;
-    static thread_local int32_t lds[HP_BOTH_LDS_WORDS];
-    for (int j = 0; j < n; ++j) dp_run_job(a, j, 0, lds);
+    EMU_LDS(lds, HP_BOTH_LDS_WORDS);
+    for (int j = 0; j < n; ++j) emu_guarded(lds, HP_LDS_WORDS, [&] { dp_run_job(a, j, 0, lds); });
     return 0;
 }
 
@@ -91,18 +115,20 @@ extern "C" int64_t emu_sort_check(int n_reads, const int64_t *seed_off, const in
 }
 
 // 1 (default): scale-1 batches take the phased path of hp_phase.h, like the product's main pass; 0: the one-kernel path
-static int g_emu_phased = 1, g_emu_unit_cap = 0, g_emu_lane_dp = 1;
+static int g_emu_phased = 1, g_emu_unit_cap = 0, g_emu_lane_dp = 1, g_emu_chain_lds_words = HP_CHAIN_LDS_WORDS;
 static long long g_emu_job_words = 0;
 extern "C" long long emu_last_job_words() { return g_emu_job_words; }      // CIGAR words the lane-per-job DP left for the fill in the last batch
 extern "C" void emu_set_lane_dp(int on) { g_emu_lane_dp = on; }           // 0: the fill runs every DP itself (one job per wave)
 extern "C" void emu_set_phased(int on) { g_emu_phased = on; }
+// LDS words of a wave of the two chaining phases: one of the three shapes of k_chain1 / k_chain2 (2432, 3392, 5120; hp_align_api.hip)
+extern "C" int emu_set_chain_lds_words(int words) { if (words < HP_SORT_BLOCK * 2 || words > EMU_CHAIN_LDS_MAX) return -1; g_emu_chain_lds_words = words; return 0; }
 extern "C" void emu_set_cl_cap(int cap) { g_emu_cl_cap = cap > 0 ? cap : (cap < 0 ? 0 : 1 << 30); }      // < 0: no clusters at all (the whole-read HBM paths)
 extern "C" void emu_set_gap_caps(int tab_cap, int mcap) { g_emu_gaptab_cap = tab_cap > 0 ? tab_cap : (tab_cap < 0 ? 0 : 1 << 30); g_emu_gap_mcap = mcap > 0 ? mcap : (mcap < 0 ? 0 : 1 << 30); }
 extern "C" void emu_set_wave_jobs(int on) { g_emu_wave_jobs = on; }
 extern "C" void emu_set_wj_small(int bytes) { g_emu_wj_small = bytes; }
 extern "C" void emu_set_pk(int on) { g_emu_pk = on; }
 extern "C" void emu_set_frag_block_min(int n) { g_emu_frag_block_min = n > 0 ? n : 3; }
-extern "C" long long emu_stat(int i) { return g_emu_stat[i & 31]; }
+extern "C" long long emu_stat(int i) { return g_emu_stat[i & 63]; }
 extern "C" void emu_dplog_on(int on) { g_emu_dplog_on = on; g_emu_dplog.clear(); }
 extern "C" long long emu_dplog(long long *buf, long long cap) { long long n = (long long)g_emu_dplog.size(); for (long long i = 0; i < n && i < cap; ++i) buf[i] = g_emu_dplog[i]; return n; }
 extern "C" void emu_stat_reset() { memset(g_emu_stat, 0, sizeof g_emu_stat); }
@@ -127,7 +153,7 @@ extern "C" int emu_align_batch(const lamsa_hp_para *P, const lamsa_hp_ref *ref, 
     a.out.stream = stream; a.out.stream_cap = stream_cap; a.out.cursor = &cursor;
     a.out.read_out_off = read_off; a.out.read_out_len = read_len; a.out.read_status = status; a.out.read_tbases = nullptr; a.out.read_work = nullptr; a.out.diag = nullptr;
     std::vector<char> slab(slab_bytes);
-    static thread_local int32_t lds[HP_BOTH_LDS_WORDS];
+    EMU_LDS(lds, EMU_CHAIN_LDS_MAX);
     if (scale == 1 && g_emu_phased) {
         // the product's main pass: chain1 -> fill -> chain2 -> fill -> publish, every phase over the whole batch before the next starts
         PhaseArgs p;
@@ -150,8 +176,9 @@ extern "C" int emu_align_batch(const lamsa_hp_para *P, const lamsa_hp_ref *ref, 
         p.wj_cap = g_emu_wave_jobs ? (int)(1024 + 64 * (int64_t)n + n_bases / 8) : 0;
         std::vector<WjRec> wjv((size_t)p.wj_cap + 1); std::vector<int32_t> wjq((size_t)WJ_NBUCKET * p.wj_cap + 1);
         p.wjobs = wjv.data(); p.wj_bucket = wjq.data();
-        static thread_local int32_t lds_lj[HP_LJ_LDS_WORDS(HP_LJ_QCAP)];
-        static thread_local int32_t lds_wj[HP_WJ_LDS_WORDS];
+        EMU_LDS(lds_lj, HP_LJ_LDS_WORDS(HP_LJ_QCAP));
+        EMU_LDS(lds_wj, HP_WJ_LDS_WORDS);
+        const int cw = g_emu_chain_lds_words;
         PhaseCtl ctl; memset(&ctl, 0, sizeof ctl);
         p.g_nd = nd.data(); p.g_nseed = nseed.data(); p.g_sidx = sidx.data(); p.meta = meta.data(); p.units = units.data(); p.bucket_q = bq.data();
         p.fl_base = fl.data(); p.line_base = lines.data(); p.ctl = &ctl;
@@ -159,20 +186,20 @@ extern "C" int emu_align_batch(const lamsa_hp_para *P, const lamsa_hp_ref *ref, 
         auto fill_all = [&](int round) {
             if (g_emu_lane_dp || g_emu_wave_jobs) {
                 for (int b = 0; b < PH_NBUCKET; ++b)
-                    for (int i = 0; i < ctl.bucket_n[round][b]; ++i) phase_filllist(p, round, bq[((size_t)round * PH_NBUCKET + b) * p.unit_cap + i], 0, lds);
+                    for (int i = 0; i < ctl.bucket_n[round][b]; ++i) emu_guarded(lds, 0, [&] { phase_filllist(p, round, bq[((size_t)round * PH_NBUCKET + b) * p.unit_cap + i], 0, lds); });      // the listing owns no LDS
                 int nw = 0, nwb = 0;
                 for (int b = 0; b < WJ_NBUCKET; ++b) { const int k = wj_queue_n(p, round, b); if (b < WJ_NBIG) nwb += k; else nw += k; }
-                for (int g = 0; g < nwb; ++g) { phase_wavejob(p, round, g, true, 0, lds_wj); ++g_emu_stat[23]; }      // the jobs that need a big slab
-                for (int g = 0; g < nw; ++g) phase_wavejob(p, round, g, false, 0, lds_wj);
+                for (int g = 0; g < nwb; ++g) { emu_guarded(lds_wj, HP_WJ_LDS_WORDS, [&] { phase_wavejob(p, round, g, true, 0, lds_wj); }); ++g_emu_stat[23]; }      // the jobs that need a big slab
+                for (int g = 0; g < nw; ++g) emu_guarded(lds_wj, HP_WJ_LDS_WORDS, [&] { phase_wavejob(p, round, g, false, 0, lds_wj); });
                 for (int b = 0; b < LJ_NBUCKET; ++b)
-                    for (int off = 0; off < lj_queue_n(p, round, b); off += 64) phase_filldp(p, round, b, off, 0, lds_lj, HP_LJ_QSMALL);
+                    for (int off = 0; off < lj_queue_n(p, round, b); off += 64) emu_guarded(lds_lj, HP_LJ_LDS_WORDS(HP_LJ_QSMALL), [&] { phase_filldp(p, round, b, off, 0, lds_lj, HP_LJ_QSMALL); });
             }
             for (int b = 0; b < PH_NBUCKET; ++b)
-                for (int i = 0; i < ctl.bucket_n[round][b]; ++i) phase_fill(p, round, bq[((size_t)round * PH_NBUCKET + b) * p.unit_cap + i], 0, lds);
+                for (int i = 0; i < ctl.bucket_n[round][b]; ++i) emu_guarded(lds, HP_LDS_WORDS, [&] { phase_fill(p, round, bq[((size_t)round * PH_NBUCKET + b) * p.unit_cap + i], 0, lds); });
         };
-        for (int r = 0; r < n; ++r) phase_chain1(p, r, 0, lds);
+        for (int r = 0; r < n; ++r) emu_guarded(lds, cw, [&] { phase_chain1(p, r, 0, lds, cw); }, g_emu_lds_shrink);
         fill_all(0);
-        for (int r = 0; r < n; ++r) phase_chain2(p, r, 0, lds);
+        for (int r = 0; r < n; ++r) emu_guarded(lds, cw, [&] { phase_chain2(p, r, 0, lds, cw); }, g_emu_lds_shrink);
         fill_all(1);
         for (int r = 0; r < n; ++r) phase_publish(p, r);
         g_emu_job_words = (long long)ctl.job_cursor;
@@ -180,7 +207,7 @@ extern "C" int emu_align_batch(const lamsa_hp_para *P, const lamsa_hp_ref *ref, 
         return 0;
     }
     a.slab = slab.data(); a.slab_per_wave = slab_bytes; a.counter = nullptr; a.order = nullptr; a.n_units = B->n_reads; a.scale = scale; a.prof = nullptr;
-    for (int r = 0; r < B->n_reads; ++r) align_read(a, r, 0, lds);
+    for (int r = 0; r < B->n_reads; ++r) emu_guarded(lds, HP_BOTH_LDS_WORDS, [&] { align_read(a, r, 0, lds); });
     *n_words = (int64_t)cursor;
     return 0;
 }
@@ -190,11 +217,11 @@ extern "C" int emu_split_indel_map(const lamsa_hp_para *P, const uint8_t *read, 
                                    int32_t *cig, int cig_cap, int32_t *ret, int32_t *status)
 {
     std::vector<char> slab((size_t)64 << 20);
-    static thread_local int32_t lds[HP_BOTH_LDS_WORDS];
+    EMU_LDS(lds, HP_BOTH_LDS_WORDS);
     Ctx cx; cx.P = P; cx.status = 0; cx.n_cells = 0; cx.lds_epoch = 0; cx.prof = nullptr; cx.lds = lds; cx.lds_words = HP_LDS_WORDS;
     arena_init(cx.tmp, slab.data(), slab.size());
     CigV out; cig_bind(out, cig, cig_cap);
-    *ret = split_indel_map(cx, out, read, read_len, ref, ref_len, ref_offset);
+    emu_guarded(lds, HP_LDS_WORDS, [&] { *ret = split_indel_map(cx, out, read, read_len, ref, ref_len, ref_offset); });
     *status = cx.status;
     return out.n;
 }
@@ -210,14 +237,14 @@ extern "C" int emu_wave_job(const lamsa_hp_para *P, int n, const uint8_t *seq, c
     std::vector<uint8_t> pac((size_t)tot / 4 + 8, 0); std::vector<int64_t> tk((size_t)n + 1, 0);
     { int64_t k = 0; for (int i = 0; i < n; ++i) { tk[i] = k; for (int j = 0; j < tlen[i]; ++j, ++k) { if (seq[t_off[i] + j] > 3) return -1; pac[k >> 2] |= (uint8_t)((seq[t_off[i] + j] & 3) << ((~k & 3) << 1)); } } }
     std::vector<char> slab(slab_bytes);
-    static thread_local int32_t lds_wj[HP_WJ_LDS_WORDS];
+    EMU_LDS(lds_wj, HP_WJ_LDS_WORDS);
     for (int i = 0; i < n; ++i) {
         Ctx cx; cx.P = P; cx.lds = lds_wj; cx.lds_words = HP_WJ_LDS_WORDS; cx.status = 0; cx.n_cells = 0; cx.lds_epoch = 0; cx.prof = nullptr;
         arena_init(cx.tmp, slab.data(), slab.size());
         const bool back = type == WJ_HEAD;
         CigV out; cig_bind(out, cig + cig_off[i], (int)(cig_off[i + 1] - cig_off[i]));
         WjOut o;
-        wj_run(cx, seq, pac.data(), type, 0, q_off[i] + (back && qlen[i] > 0 ? qlen[i] - 1 : 0), back ? -1 : 1, qlen[i], tk[i] + (back && tlen[i] > 0 ? tlen[i] - 1 : 0), back ? -1 : 1, tlen[i], w, h0, out, o);
+        emu_guarded(lds_wj, HP_WJ_LDS_WORDS, [&] { wj_run(cx, seq, pac.data(), type, 0, q_off[i] + (back && qlen[i] > 0 ? qlen[i] - 1 : 0), back ? -1 : 1, qlen[i], tk[i] + (back && tlen[i] > 0 ? tlen[i] - 1 : 0), back ? -1 : 1, tlen[i], w, h0, out, o); });
         score[i] = o.score; qle[i] = o.qle; tle[i] = o.tle; status[i] = cx.status; cig_n[i] = out.n;
     }
     return 0;
@@ -235,12 +262,13 @@ extern "C" int emu_lane_dp(const lamsa_hp_para *P, int n, const uint8_t *seq, co
     { int64_t k = 0; for (int i = 0; i < n; ++i) { tk[i] = k; for (int j = 0; j < tlen[i]; ++j, ++k) pac[k >> 2] |= (uint8_t)((seq[t_off[i] + j] & 3) << ((~k & 3) << 1)); } }
     std::vector<uint8_t> z((size_t)HP_LJ_QCAP * HP_LJ_TCAP * 64 + 64);
     std::vector<cig_t> cb((size_t)3 * HP_LJ_CIG * 64);
-    static thread_local int32_t lds_lj[HP_LJ_LDS_WORDS(HP_LJ_QCAP)];
+    EMU_LDS(lds_lj, HP_LJ_LDS_WORDS(HP_LJ_QCAP));
     if (!lj_params_ok(P)) return -2;
-    for (int j0 = 0; j0 < n; j0 += 64) {
+    int rc = 0;
+    for (int j0 = 0; j0 < n && rc == 0; j0 += 64) emu_guarded(lds_lj, HP_LJ_LDS_WORDS(HP_LJ_QCAP), [&] {
         for (int l = 0; l < 64 && j0 + l < n; ++l) {
             const int i = j0 + l;
-            if (qlen[i] > HP_LJ_QCAP || tlen[i] > HP_LJ_TCAP) return -1;
+            if (qlen[i] > HP_LJ_QCAP || tlen[i] > HP_LJ_TCAP) { rc = -1; return; }
             LaneJob J; J.q = seq + q_off[i]; J.qs = 1; J.qcomp = 0; J.qlen = qlen[i]; J.pac = pac.data(); J.tk = tk[i]; J.ts = 1; J.tlen = tlen[i]; J.z = z.data(); J.zl = l; J.zs = HP_LJ_QCAP; J.cells = 0;
             J.row = lds_lj + l; J.qrow = (uint8_t *)(lds_lj + (HP_LJ_QCAP + 2) * 64) + l; J.rev = 0;
             lj_stage_query(J);
@@ -252,6 +280,6 @@ extern "C" int emu_lane_dp(const lamsa_hp_para *P, int n, const uint8_t *seq, co
             qle[i] = a; tle[i] = b; cig_n[i] = out.n;
             memcpy(cig + (size_t)i * HP_LJ_CIG, out.c, sizeof(cig_t) * (size_t)out.n);
         }
-    }
-    return 0;
+    });
+    return rc;
 }

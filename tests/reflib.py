@@ -445,18 +445,36 @@ def end_extension_from_oracle(jobs, lp, head, w, h0):
     return dict(score=want["score"], qle=want["qle"], tle=want["tle"], cigars=cigs)
 
 
-def emu_streams(batch, hp_para, scale=1, slab_bytes=256 << 20, phased=True, unit_cap=0, cl_cap=0, lane_dp=True, gaptab_cap=0, gap_mcap=0, stats=None, wave_jobs=True, wj_small=0, frag_block_min=0):
+CHAIN_LDS_WORDS = (2432, 3392, 5120)          # LDS words per wave of the three shapes of the chaining kernels (hp_align_api.hip: g_chain_shapes)
+N_STATS = 64
+
+
+def emu_guard_hits(E=None):
+    """Phase calls of the emulation that wrote into the 64 guard words behind their LDS since the last emu_streams / reset."""
+    E = E or emu()
+    E.emu_lds_guard_hits.restype = C.c_longlong
+    return int(E.emu_lds_guard_hits())
+
+
+def emu_streams(batch, hp_para, scale=1, slab_bytes=256 << 20, phased=True, unit_cap=0, cl_cap=0, lane_dp=True, gaptab_cap=0, gap_mcap=0, stats=None, wave_jobs=True, wj_small=0, frag_block_min=0,
+                chain_lds_words=2432, lds_shrink=0, guard=None):
     """Per-read result streams from the device sources compiled with the CPU lane emulation.
     phased: scale-1 batches go through the launches of hp_phase.h (the product's main pass) instead of the one-kernel path.
     cl_cap: clusters of more hits than this take the HBM path of the main chaining pass instead of the LDS one (hp_cluster.h).
     gaptab_cap / gap_mcap: reads with more seed slots scan the gaps of a line by seed range instead of by cluster / gaps with more
     survivors take the wave-wide mini DP (hp_gaps.h); < 0 = none qualifies.  wave_jobs: False = no wave-per-job launch (hp_wavejob.h), the fill
     runs the junctions beyond a lane job and the end extensions itself; wj_small: the ordinary slab of a wave job in bytes (jobs that need more go to
-    the waves that own a big slab).  stats: a list that receives the HP_STAT path counters."""
+    the waves that own a big slab).  stats: a list that receives the HP_STAT path counters (slots: hp_core.h).
+    chain_lds_words: LDS words of a wave of the two chaining phases (one of CHAIN_LDS_WORDS, the shapes of k_chain1 / k_chain2; the one-kernel
+    path always has HP_BOTH_LDS_WORDS).  Every LDS buffer handed to a phase is followed by guard words that are checked after every call: the
+    number of damaged checks must be 0.  lds_shrink (tests of the guards themselves): the guards of the two chaining phases start that many words INSIDE the
+    LDS the phase is told it owns; guard: a list that then receives the number of damaged checks instead of the assertion."""
     from lamsa_amd.hp import HpRef, HpBatch
     E = emu()
     E.emu_set_phased(1 if phased else 0); E.emu_set_unit_cap(int(unit_cap)); E.emu_set_cl_cap(int(cl_cap)); E.emu_set_lane_dp(1 if lane_dp else 0)
     E.emu_set_gap_caps(int(gaptab_cap), int(gap_mcap)); E.emu_set_wave_jobs(1 if wave_jobs else 0); E.emu_set_wj_small(int(wj_small)); E.emu_set_frag_block_min(int(frag_block_min)); E.emu_stat_reset(); E.emu_stat.restype = C.c_longlong
+    assert E.emu_set_chain_lds_words(int(chain_lds_words)) == 0, chain_lds_words
+    E.emu_set_lds_shrink(int(lds_shrink)); E.emu_lds_guard_reset()
     n = batch.n_reads
     hb = hp_batch_struct(batch, HpBatch)
     hr = HpRef(batch.pac.ctypes.data, int(batch.l_pac), len(batch.seq_len), batch.seq_off.ctypes.data, batch.seq_len.ctypes.data)
@@ -466,8 +484,14 @@ def emu_streams(batch, hp_para, scale=1, slab_bytes=256 << 20, phased=True, unit
     E.emu_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     E.emu_align_batch(C.byref(hp_para), C.byref(hr), C.byref(hb), scale, slab_bytes, stream.ctypes.data, cap, C.byref(nw), off.ctypes.data, ln.ctypes.data, st.ctypes.data)
     if stats is not None:
-        stats[:] = [int(E.emu_stat(i)) for i in range(32)]
+        stats[:] = [int(E.emu_stat(i)) for i in range(N_STATS)]
     E.emu_set_gap_caps(0, 0); E.emu_set_wave_jobs(1); E.emu_set_wj_small(0); E.emu_set_frag_block_min(0)
+    E.emu_set_chain_lds_words(CHAIN_LDS_WORDS[0]); E.emu_set_lds_shrink(0)
+    hits = emu_guard_hits(E)
+    if guard is not None:
+        guard[:] = [hits]
+    else:
+        assert hits == 0, "%d phase calls of the emulation wrote behind their LDS" % hits
     return split_streams(stream, off[:n], ln[:n]), st[:n].copy()
 
 
