@@ -153,10 +153,16 @@ typedef struct lamsa_hp_batch {
  *   per res  : offset_lo, offset_hi, chr, nstrand (1 '+', 0 '-'), score (AS), NM, cigar_n, cigar words...
  *              and, only with LAMSA_HP_TAG_MISMATCHES set (lamsa_hp_set_result_tags), after the CIGAR words:
  *              n_mm, then n_mm words ref_off << 2 | base, ref_off ascending
+ *              With LAMSA_HP_TAG_EQX set, cigar_n and the CIGAR words are the =/X form (below); no other word changes.
  * i.e. the fields of line_aln_res / res_t (src/frag_check.h:46-73) that aln_res_output and
  * rearr_aln_res consume.  A mismatch word names one aligned base that differs from the reference: ref_off is its
  * 0-based offset from the record's offset (POS) on the forward reference, base the .pac code (0-3) of the reference
- * base there.  A read N (code 4) is a mismatch, as it is for NM; so NM = n_mm + inserted + deleted bases. */
+ * base there.  A read N (code 4) is a mismatch, as it is for NM; so NM = n_mm + inserted + deleted bases.
+ * The =/X form of a CIGAR (ops numbered as in SAM: '=' is 7, 'X' is 8): every M element is replaced, on its own, by its
+ * pieces -- the maximal runs of aligned bases that equal the reference ('=') or differ from it ('X'; a read N differs).
+ * The pieces are in order, none is empty, neighbours alternate; every other element is copied as it is, and pieces never
+ * merge across elements ("..1X 2I 1X.." stays three elements).  So the X lengths of a record sum to its n_mm, the pieces
+ * of one element with 7/8 read as 0 add up to the original word, and a record has at most cigar_n + 2 n_mm words. */
 typedef struct lamsa_hp_result {
     const int32_t *stream; int64_t stream_words;
     const int64_t *read_off;      /* [n_reads] start of read r's stream */
@@ -171,8 +177,11 @@ int lamsa_hp_align_batch(lamsa_hp_handle *h, const lamsa_hp_batch *batch, lamsa_
 
 /* Optional items of the result stream (lamsa_hp_result), for the batches aligned after the call; 0 (the default) is the
  * stream as documented without them.  LAMSA_HP_TAG_MISMATCHES: every record also lists its mismatches (what a SAM
- * writer needs for MD:Z without reading the reference again).  LAMSA_HP_EINVAL while a batch or run is in flight. */
+ * writer needs for MD:Z without reading the reference again).  LAMSA_HP_TAG_EQX: the CIGARs are in =/X form (the
+ * device splits the M elements by the same lists, which are in the stream only if LAMSA_HP_TAG_MISMATCHES is set too).
+ * flags outside LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX: LAMSA_HP_EINVAL; so while a batch or run is in flight. */
 #define LAMSA_HP_TAG_MISMATCHES 1
+#define LAMSA_HP_TAG_EQX 2
 int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags);
 
 /* The same in two steps, so that a caller can keep a batch resident in HBM and overlap or

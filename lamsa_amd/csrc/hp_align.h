@@ -3,6 +3,7 @@
 // worker lamsa_main_aln (src/lamsa_aln.c:857-871), minus stage (4)/(5)/(6) which stay on the host.
 #pragma once
 #include "hp_fill.h"
+#include "hp_eqx.h"
 #include "hp_sort.h"
 
 namespace hp {
@@ -73,18 +74,26 @@ HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
     for (int j = 0; j <= la.cur_res_n; ++j) {
         const Rec &rec = la.rec[j];
         out_put(cx, o, (int32_t)(rec.offset & 0xffffffffll)); out_put(cx, o, (int32_t)(rec.offset >> 32));
-        out_put(cx, o, rec.chr); out_put(cx, o, rec.nstrand); out_put(cx, o, rec.score); out_put(cx, o, rec.NM); out_put(cx, o, rec.cig.n);
-        if (o.n + rec.cig.n <= o.cap) {                               // the record's CIGAR, copied by the lanes (word by word it was 2 500 dependent trips per line: 14 % of the fill kernel)
-            HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
-            const HP_G cig_t *src = (const HP_G cig_t *)rec.cig.c;
-            const int cn = rec.cig.n;
-            wv::sync();
-            for (int b0 = 0; b0 < cn; b0 += 64) { WAVE_FOR(l) { const int k = b0 + l; if (k < cn) dst[k] = (int32_t)src[k]; } }
-            o.n += cn;
-            wv::sync();
+        out_put(cx, o, rec.chr); out_put(cx, o, rec.nstrand); out_put(cx, o, rec.score); out_put(cx, o, rec.NM);
+        if (la.tags & LAMSA_HP_TAG_EQX) {                             // the CIGAR in =/X form (hp_eqx.h): cigar_n is known once the words are written
+            const int n = o.n < o.cap ? eqx_words(rec.cig.c, rec.cig.n, rec.mm, rec.n_mm, o.w + o.n + 1, o.cap - o.n - 1) : -1;
+            if (n >= 0) { o.w[o.n] = n; o.n += 1 + n; }
+            else cx.status |= ST_OVERFLOW;
         }
-        else cx.status |= ST_OVERFLOW;
-        if (la.ev) {                                                  // LAMSA_HP_TAG_MISMATCHES: the record's mismatch list (res_aux)
+        else {
+            out_put(cx, o, rec.cig.n);
+            if (o.n + rec.cig.n <= o.cap) {                           // the record's CIGAR, copied by the lanes (word by word it was 2 500 dependent trips per line: 14 % of the fill kernel)
+                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
+                const HP_G cig_t *src = (const HP_G cig_t *)rec.cig.c;
+                const int cn = rec.cig.n;
+                wv::sync();
+                for (int b0 = 0; b0 < cn; b0 += 64) { WAVE_FOR(l) { const int k = b0 + l; if (k < cn) dst[k] = (int32_t)src[k]; } }
+                o.n += cn;
+                wv::sync();
+            }
+            else cx.status |= ST_OVERFLOW;
+        }
+        if (la.tags & LAMSA_HP_TAG_MISMATCHES) {                      // the record's mismatch list (res_aux)
             const int nm = rec.n_mm;
             out_put(cx, o, nm);
             if (o.n + nm <= o.cap) {
@@ -100,12 +109,15 @@ HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
     }
 }
 
-// LAMSA_HP_TAG_MISMATCHES: the mismatch lists of a line (LineRes::ev) -- at most one per aligned read base, the records of a line
-// cover disjoint parts of the read -- and what they add to the line's result words (the lists and a count per record)
+// The mismatch lists of a line (LineRes::ev, made under any LAMSA_HP_TAG_* item) -- at most one per aligned read base, the records of a
+// line cover disjoint parts of the read -- and what the items add to the line's result words: LAMSA_HP_TAG_MISMATCHES the lists and a
+// count per record, LAMSA_HP_TAG_EQX at most two words per mismatch (a record has at most cigar_n + 2 n_mm words, hp_eqx.h)
 HP_INL int line_ev_cap(int L) { return L + 64; }
 HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
+HP_INL int line_eqx_words(int L) { return 2 * (L + 64); }
+HP_INL int line_tag_words(int L, int tags) { return ((tags & LAMSA_HP_TAG_MISMATCHES) ? line_ev_words(L) : 0) + ((tags & LAMSA_HP_TAG_EQX) ? line_eqx_words(L) : 0); }
 // words of a read's result stream on the one-kernel path (align_read); the second pass sizes its arena by it
-HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + (tags ? 4LL * L + 4 * HP_REC_MAX : 0)) * scale; }
+HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + ((tags & LAMSA_HP_TAG_MISMATCHES) ? 4LL * L + 4 * HP_REC_MAX : 0) + ((tags & LAMSA_HP_TAG_EQX) ? 8LL * L + 512 : 0)) * scale; }
 
 // frag_check over all lines of one round (frag_check.c:886-955) + get_reg (lamsa_aln.c:597) for round 1
 HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
@@ -119,7 +131,7 @@ HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int re
     const int ev_cap = tags ? line_ev_cap(r.L) * scale : 0;
     int32_t *ev = tags ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)ev_cap) : nullptr;
     if (!la || !cur_buf || !rec_buf || (tags && !ev)) { arena_release(cx.tmp, mark); return; }
-    la->ev = ev; la->ev_cap = ev_cap;
+    la->ev = ev; la->ev_cap = ev_cap; la->tags = tags;
     for (int j = 0; j < F.n; ++j) {
         if (!fill_line(r, F, j, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX)) break;
         out_line(cx, o, *la);
@@ -230,7 +242,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
     if (skip) { cx.status |= ST_UNSUPPORTED; r.H = 0; r.seed_out = 0; }
     const int H = r.H;
     // read-lifetime allocations
-    const int tags = a.in.tags & LAMSA_HP_TAG_MISMATCHES;
+    const int tags = a.in.tags & (LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX);
     const int out_cap = (int)read_out_cap(r.L, a.scale, tags);
     OutBuf o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);

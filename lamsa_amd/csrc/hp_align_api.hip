@@ -340,12 +340,16 @@ static int grow(lamsa_hp_handle *h, DevBuf &b, size_t bytes)
     return b.ensure(bytes);
 }
 
+// result + CIGAR bytes per read base of a wave's scratch; `eqx`: what the =/X words of LAMSA_HP_TAG_EQX add (a line's: 2 words per base,
+// line_eqx_words; a read's on the one-kernel path: 8, read_out_cap)
+static size_t tag_slab_per_base(int tags, int eqx) { return (size_t)(tags ? 152 : 128) + ((tags & LAMSA_HP_TAG_EQX) ? (size_t)eqx : 0); }
 static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale, int tags)
 {   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base; 24 more with the
-    // mismatch lists of LAMSA_HP_TAG_MISMATCHES), and the direction matrix of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
+    // mismatch lists of any LAMSA_HP_TAG_* item, 40 more for the =/X words of LAMSA_HP_TAG_EQX: read_out_cap), and the direction matrix
+    // of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
     // Reads that need more flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
     const size_t z = (2 * (size_t)P.band_w + 128) * ((size_t)L + 256);
-    return al256(((size_t)256 << 10) + (size_t)scale * (tags ? 152 : 128) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
+    return al256(((size_t)256 << 10) + (size_t)scale * tag_slab_per_base(tags, 40) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
 }
 
 // validate `B`, build its processing order and sort index, copy it into slot `T` on the copy stream
@@ -560,8 +564,12 @@ static PhasedLayout phased_layout(int n, int64_t n_hits, int64_t n_bases, int64_
     Y.bytes = off;
     return Y;
 }
-// words of a batch's result stream; the mismatch lists (LAMSA_HP_TAG_MISMATCHES) are at most one word per aligned base and a count per record
-static int64_t main_stream_cap(int n, int64_t n_bases, int tags) { return 1024 + (int64_t)n * 256 + 4 * n_bases + (tags ? (int64_t)n * 128 + 2 * n_bases : 0); }
+// words of a batch's result stream; the mismatch lists (LAMSA_HP_TAG_MISMATCHES) are at most one word per aligned base and a count per record,
+// the =/X pieces (LAMSA_HP_TAG_EQX) at most two words per aligned base
+static int64_t main_stream_cap(int n, int64_t n_bases, int tags)
+{
+    return 1024 + (int64_t)n * 256 + 4 * n_bases + ((tags & LAMSA_HP_TAG_MISMATCHES) ? (int64_t)n * 128 + 2 * n_bases : 0) + ((tags & LAMSA_HP_TAG_EQX) ? (int64_t)n * 128 + 4 * n_bases : 0);
+}
 
 // The main pass of the batch in slot `T` as the five launches of hp_phase.h, with the launch resources of slot `Ln`.
 // scratch of a wave of each kind of launch (all launches of a batch share one allocation, one after the other): the chaining launches keep
@@ -593,7 +601,7 @@ static SlabPlan slab_plan(lamsa_hp_handle *h, int max_L, int max_H, bool shared 
     // itself, a lane-DP group's buffers.  Wave jobs: an ordinary slab takes the junctions and the end extensions of a few thousand rows; the
     // direction matrix of the longest end extension (the whole read long) lives in one of the big slabs that only the first waves own.
     Q.chain = al256(((size_t)256 << 10) + 128 * (size_t)max_L + 424 * (size_t)max_H);
-    Q.fill = al256(((size_t)256 << 10) + (h->result_tags ? 152 : 128) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
+    Q.fill = al256(((size_t)256 << 10) + tag_slab_per_base(h->result_tags, 16) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
     { static const int kb = getenv("LAMSA_HP_WJ_SLAB_KB") ? atoi(getenv("LAMSA_HP_WJ_SLAB_KB")) : 0;    // diagnostic
       Q.wj = ((size_t)(kb > 0 ? kb : 1024) << 10) + 33 * 256; }
     Q.wjb = al256((size_t)wj_need(&P, WJ_HEAD, max_L, max_L + 2 * P.hash_step + 64) + ((size_t)64 << 10)) + 33 * 256;
@@ -966,7 +974,7 @@ extern "C" int lamsa_hp_set_scratch_limit(lamsa_hp_handle *h, size_t bytes)
 
 extern "C" int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags)
 {
-    if (!h || (flags & ~LAMSA_HP_TAG_MISMATCHES)) return LAMSA_HP_EINVAL;
+    if (!h || (flags & ~(LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX))) return LAMSA_HP_EINVAL;
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight: collect them first"; return LAMSA_HP_EINVAL; }
     h->result_tags = flags;

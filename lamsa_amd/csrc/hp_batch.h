@@ -34,7 +34,7 @@ struct BatchIn {
     const int8_t  *h_strand;     // +1 / -1
     const uint8_t *h_cig_n;
     const int32_t *cig;          // seed CIGAR words
-    int32_t tags = 0;            // LAMSA_HP_TAG_* items of the result stream (0: none; callers that build a BatchIn field by field leave it so)
+    int32_t tags = 0;            // LAMSA_HP_TAG_* items of the result stream (0: none; callers that build a BatchIn field by field leave it so); wave-uniform
 };
 
 // Result stream of one read (int32 words), serialised by the wave that aligned it:
@@ -42,6 +42,8 @@ struct BatchIn {
 //   per line : line_score, tol_score, tol_NM, n_res
 //   per res  : offset_lo, offset_hi, chr, nstrand(1 '+', 0 '-'), score(AS), NM, cigar_n, cigar words...
 //              [in.tags & LAMSA_HP_TAG_MISMATCHES] n_mm, n_mm words ref_off << 2 | base (res_aux, hp_fill.h)
+//              [in.tags & LAMSA_HP_TAG_EQX] cigar_n and the cigar words are the =/X form: every M split into its '=' (7) and 'X' (8) pieces
+//              by eqx_words (hp_eqx.h) from the same lists, which are shipped only under LAMSA_HP_TAG_MISMATCHES
 struct BatchOut {
     int32_t *stream;             // global result arena
     int64_t stream_cap;          // words

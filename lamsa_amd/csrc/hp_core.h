@@ -8,7 +8,7 @@
 namespace hp {
 
 typedef int32_t cig_t;                       // len<<4|op, signed like the reference (src/lamsa_aln.h:210)
-enum { C_M = 0, C_I = 1, C_D = 2, C_N = 3, C_S = 4, C_H = 5 };
+enum { C_M = 0, C_I = 1, C_D = 2, C_N = 3, C_S = 4, C_H = 5, C_EQ = 7, C_X = 8 };      // numbered as in SAM; '=' and 'X' only in the result stream (LAMSA_HP_TAG_EQX, hp_eqx.h)
 enum { ST_OVERFLOW = LAMSA_HP_ST_OVERFLOW, ST_REFEXIT = LAMSA_HP_ST_REFEXIT, ST_UNSUPPORTED = LAMSA_HP_ST_UNSUPPORTED,
        ST_DEAD = ST_OVERFLOW | ST_REFEXIT | ST_UNSUPPORTED };     // ST_DEAD: the read has no result
 

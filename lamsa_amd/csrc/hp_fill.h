@@ -29,7 +29,8 @@ struct Rec {                     // res_t, frag_check.h:46-59
 };
 struct LineRes {                 // line_aln_res, frag_check.h:61-73
     int line_score, tol_score, tol_NM, cur_res_n;
-    int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (LAMSA_HP_TAG_MISMATCHES), or nullptr
+    int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (any LAMSA_HP_TAG_* item needs them), or nullptr
+    int tags;                    // set by the caller: the LAMSA_HP_TAG_* items out_line writes (lists shipped / CIGARs in =/X form)
     Rec rec[HP_REC_MAX];
 };
 

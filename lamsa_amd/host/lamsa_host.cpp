@@ -624,6 +624,34 @@ static void host_mismatches(ReadResult &R, const uint8_t *bseq, int read_len, co
             }
 }
 
+void rec_to_eqx(Rec &r)
+{
+    std::vector<int32_t> out;
+    out.reserve(r.cigar.size() + 2 * r.mm.size());
+    int64_t ref = 0; size_t e = 0;
+    for (int32_t w : r.cigar) {
+        const int op = w & 0xf, len = w >> 4;
+        if (op == 0) {
+            const int64_t end = ref + len;
+            while (e < r.mm.size() && (r.mm[e] >> 2) < end) {
+                const int64_t p = r.mm[e] >> 2;
+                size_t j = e;                                    // the run of neighbouring mismatches that starts here (it ends with the element)
+                while (j + 1 < r.mm.size() && (r.mm[j + 1] >> 2) == (r.mm[j] >> 2) + 1 && (r.mm[j + 1] >> 2) < end) ++j;
+                if (p > ref) out.push_back((int32_t)((p - ref) << 4) | 7);
+                out.push_back((int32_t)((j - e + 1) << 4) | 8);
+                ref = p + (int64_t)(j - e + 1); e = j + 1;
+            }
+            if (end > ref) out.push_back((int32_t)((end - ref) << 4) | 7);
+            ref = end;
+        } else {
+            out.push_back(w);
+            if (op == 2) ref += len;
+            else if (op == 7 || op == 8) { ref += len; while (e < r.mm.size() && (r.mm[e] >> 2) < ref) ++e; }      // in =/X form already
+        }
+    }
+    r.cigar.swap(out);
+}
+
 // a stable sort that allocates nothing for the handful of elements a read has (std::stable_sort asks for a buffer every time)
 template <class It, class Less> static inline void small_stable_sort(It b, It e, Less less)
 {
@@ -768,7 +796,7 @@ static void append_md(std::string &o, const Rec &r, const Index &ix)
     int64_t ref = 0; int run = 0; size_t e = 0;
     for (int32_t w : r.cigar) {
         const int op = w & 0xf, len = w >> 4;
-        if (op == 0) {
+        if (cig_aligned(op)) {                         // aligned bases, in M or in =/X form
             const int64_t end = ref + len;
             for (; e < r.mm.size() && (r.mm[e] >> 2) < end; ++e) {
                 const int64_t p = r.mm[e] >> 2;
@@ -782,6 +810,42 @@ static void append_md(std::string &o, const Rec &r, const Index &ix)
         }                                                           // I, S, H: nothing of the reference
     }
     append_int(o, run);
+}
+
+// cs:Z of a record, minimap2's short form: ":n" identical bases, "*xy" a substitution (reference base, read base), "+seq" inserted read
+// bases, "-seq" deleted reference bases; lowercase, a read N is 'n', everything on the forward reference strand (as SEQ is printed); clips
+// contribute nothing.  The substituted reference bases come from the mismatch list, the deleted ones from the .pac (MD's caveat on N holds).
+static void append_cs(std::string &o, const Rec &r, const Read &rd, const Index &ix)
+{
+    static const char B[] = "acgt";
+    const int read_len = (int)rd.seq.size();
+    auto base = [&](int i) {                                          // base i of the read as the record aligns it
+        switch (r.nstrand == 1 ? rd.seq[(size_t)i] : comp_char(rd.seq[(size_t)(read_len - 1 - i)])) {
+            case 'A': case 'a': return 'a'; case 'C': case 'c': return 'c'; case 'G': case 'g': return 'g'; case 'T': case 't': return 't'; default: return 'n'; }
+    };
+    const int64_t k0 = ix.off[(size_t)r.chr - 1] + r.offset - 1;
+    int64_t ref = 0; int read_i = 0; size_t e = 0;
+    for (int32_t w : r.cigar) {
+        const int op = w & 0xf, len = w >> 4;
+        if (cig_aligned(op)) {
+            const int64_t beg = ref, end = ref + len;
+            for (; e < r.mm.size() && (r.mm[e] >> 2) < end; ++e) {
+                const int64_t p = r.mm[e] >> 2;
+                if (p > ref) { o.push_back(':'); append_int(o, (long long)(p - ref)); }
+                o.push_back('*'); o.push_back(B[r.mm[e] & 3]); o.push_back(base(read_i + (int)(p - beg)));
+                ref = p + 1;
+            }
+            if (end > ref) { o.push_back(':'); append_int(o, (long long)(end - ref)); }
+            ref = end; read_i += len;
+        } else if (op == 1) {
+            o.push_back('+');
+            for (int j = 0; j < len; ++j) o.push_back(base(read_i + j));
+            read_i += len;
+        } else if (op == 2) {
+            o.push_back('-');
+            for (int j = 0; j < len; ++j, ++ref) { const int64_t k = k0 + ref; o.push_back(B[ix.pac[(size_t)(k >> 2)] >> ((~k & 3) << 1) & 3]); }
+        } else if (op == 4) read_i += len;
+    }
 }
 
 void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index &ix, const Options &opt)
@@ -836,6 +900,7 @@ void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index 
                     }
                 }
                 if (opt.tag_md) { o += "\tMD:Z:"; append_md(o, r, ix); }
+                if (opt.tag_cs) { o += "\tcs:Z:"; append_cs(o, r, rd, ix); }
                 if (sa.size() > 1) { o += "\tSA:Z:"; for (size_t k = 0; k < sa.size(); ++k) if (k != (size_t)all - 1) o += sa[k]; }
                 o.push_back('\n');
             }
@@ -1079,11 +1144,15 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     if (rc != LAMSA_HP_OK) for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh);
     const int G = (int)std::max<size_t>(1, hs.size());
     if (rc != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] no usable MI355X / HIP device (lamsa_hp_create: %d); this build has no CPU path\n", rc); return 2; }
-    // --MD: every handle lists the mismatches of its records in the result stream
-    const bool dev_mm = opt.tag_md && lamsa_hp_set_result_tags != nullptr;
+    // --MD, --cs: every handle lists the mismatches of its records in the result stream; --eqx: it writes the CIGARs in =/X form.  Against
+    // a library without lamsa_hp_set_result_tags the host makes the lists (host_mismatches) and the =/X form (rec_to_eqx) itself.
+    const bool need_mm = opt.tag_md || opt.tag_cs;
+    const int dev_tags = lamsa_hp_set_result_tags != nullptr ? (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) : 0;
+    const bool dev_mm = (dev_tags & LAMSA_HP_TAG_MISMATCHES) != 0;
+    const bool host_mm = (need_mm || opt.tag_eqx) && lamsa_hp_set_result_tags == nullptr, host_eqx = opt.tag_eqx && !(dev_tags & LAMSA_HP_TAG_EQX);
     for (lamsa_hp_handle *hh : hs) {
-        if (!dev_mm) break;
-        const int e = lamsa_hp_set_result_tags(hh, LAMSA_HP_TAG_MISMATCHES);
+        if (!dev_tags) break;
+        const int e = lamsa_hp_set_result_tags(hh, dev_tags);
         if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_set_result_tags failed: %d %s\n", e, lamsa_hp_last_error(hh)); for (lamsa_hp_handle *x : hs) lamsa_hp_destroy(x); return 2; }
     }
     // stage (4): needs the reference's FM index files and a second handle for its DP batches (a handle is single-threaded)
@@ -1320,7 +1389,8 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
                 parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm);
-                if (opt.tag_md && !dev_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
+                if (host_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
+                if (host_eqx && R.status == 0) for (int st = 0; st < 2; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) rec_to_eqx(x);
                 if (rescue && R.status == 0) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
             }
         });
@@ -1359,7 +1429,10 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             for (int r = t_first[(size_t)t]; r < t_last[(size_t)t]; ++r) {
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
-                if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp);
+                if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) {
+                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp);
+                    if (opt.tag_eqx) for (Line &ln : R.stage[2]) for (Rec &x : ln.rec) rec_to_eqx(x);       // stage-4 records are made on the host, with their lists (rec_aux)
+                }
                 if (R.status != 0) {
                     ++bad_of[(size_t)t];
                     fprintf(stderr, "[lamsa_aln] read %s: %s; reported unmapped\n", B.reads[(size_t)r].name.c_str(), (R.status & LAMSA_HP_ST_UNSUPPORTED) ? "more than 32767 seeds, or a seed hit with |len_dif| > 127: beyond what the device keeps" : (R.status & LAMSA_HP_ST_REFEXIT) ? "input on which the reference aligner exits" : "device work buffer overflow");

@@ -61,8 +61,10 @@ struct Batch {                       // the arrays of lamsa_hp_batch, host side
     void clear();
 };
 
+// cigar: M form, or with --eqx the =/X form (ops 7 / 8): every routine that walks it takes 0, 7 and 8 alike, as read and reference bases
+inline bool cig_aligned(int op) { return op == 0 || op == 7 || op == 8; }      // M, =, X: read and reference bases facing each other
 struct Rec { int64_t offset = 0; int chr = 0, nstrand = 0, score = 0, NM = 0, reg_beg = 0, reg_end = 0; std::vector<int32_t> cigar;   // res_t
-             std::vector<int32_t> mm; };     // --MD: the mismatches, ref_off << 2 | base (include/lamsa_hp.h, LAMSA_HP_TAG_MISMATCHES)
+             std::vector<int32_t> mm; };     // --MD, --cs: the mismatches, ref_off << 2 | base (include/lamsa_hp.h, LAMSA_HP_TAG_MISMATCHES)
 struct XaRef { int st, li, ri; };
 struct Line { int line_score = 0, tol_score = 0, tol_NM = 0, merg_x = 0, merg_y = 0; uint8_t mapQ = 0; std::vector<Rec> rec; std::vector<XaRef> xa; };   // line_aln_res
 struct ReadResult { int status = 0; std::vector<Line> stage[3]; };   // aln_res[3]: first round, remain round, BWT rescue (empty)
@@ -70,6 +72,9 @@ struct ReadResult { int status = 0; std::vector<Line> stage[3]; };   // aln_res[
 // with_mm: the stream carries the records' mismatch lists (lamsa_hp_set_result_tags(h, LAMSA_HP_TAG_MISMATCHES))
 void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm = false);
 void rank_results(ReadResult &R, int read_len, const lamsa_hp_para &P);
+// the record's CIGAR into =/X form from its mismatch list, to the definition of include/lamsa_hp.h (what the device does under
+// LAMSA_HP_TAG_EQX): for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host
+void rec_to_eqx(Rec &r);
 
 // a path as one word of a POSIX shell command line: wrapped in single quotes, embedded ones spelled '\''
 inline std::string shell_quote(const std::string &p) { std::string o = "'"; for (char c : p) { if (c == '\'') o += "'\\''"; else o += c; } return o + "'"; }
@@ -88,6 +93,7 @@ struct Options {
                                                           // the outputs of shards 0 .. N-1 concatenated are the unsharded output (only shard 0 writes the header)
     int parse_only = 0;                                   // --parse-only: read and parse the inputs, no GPU work, no output (ingest timing)
     int tag_md = 0, tag_sa = 0;                           // --MD, --SA: MD:Z / SA:Z at the end of every mapped record (not in the reference's output)
+    int tag_eqx = 0, tag_cs = 0;                          // --eqx: every printed CIGAR in =/X form (LAMSA_HP_TAG_EQX, include/lamsa_hp.h); --cs: cs:Z (short form) on every mapped record
     float ed_rate = -1, mis_rate = -1, mat_rate = -1;     // -e, -x; defaults per read type (src/lamsa_aln.h:26-70)
     std::string gem_dir;                                  // directory holding gem-mapper (default: <directory of this binary>/gem)
     int chunk_reads = 16384; int64_t chunk_bases = 256ll << 20;     // reads per GPU batch (the reference's CHUNK_READ_N is 128 per thread pool)

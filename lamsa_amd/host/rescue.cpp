@@ -118,7 +118,7 @@ struct Reg { int beg, end; std::vector<RegB> rb, re; };
 int ref_in_cigar(const std::vector<int32_t> &c)
 {   // refInCigar, src/frag_check.c:205 (H counts as reference there)
     int n = 0;
-    for (int32_t w : c) { const int op = w & 0xf; if (op == 0 || op == 2 || op == 5) n += w >> 4; }
+    for (int32_t w : c) { const int op = w & 0xf; if (cig_aligned(op) || op == 2 || op == 5) n += w >> 4; }      // (=/X: a record of --eqx)
     return n;
 }
 
@@ -399,7 +399,7 @@ bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts
     r.mm.clear();
     for (size_t i = 0; ok && i < r.cigar.size(); ++i) {
         const int op = r.cigar[i] & 0xf, len = r.cigar[i] >> 4;
-        if (op == 0) {
+        if (cig_aligned(op)) {                        // aligned bases, in M or in =/X form
             if (read_i + len > read_len || ref_i + len > ref_len) { ok = false; break; }
             int mm = 0;
             for (int j = 0; j < len; ++j, ++read_i, ++ref_i) if (rd[read_i] != ref[(size_t)ref_i]) { ++mm; r.mm.push_back(ref_i << 2 | ref[(size_t)ref_i]); }
@@ -462,7 +462,7 @@ void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index
         bool accept = true;
         if (P.read_type > 0) {                                  // solid_readInCigar(...) > 0.5 * reg_len, :376
             int solid = 0;
-            for (int32_t w : r.cigar) { const int op = w & 0xf; if (op == 0 || op == 1) solid += w >> 4; }
+            for (int32_t w : r.cigar) { const int op = w & 0xf; if (cig_aligned(op) || op == 1) solid += w >> 4; }
             accept = (double)solid > 0.5 * L.reg_len;
         }
         if (accept) {

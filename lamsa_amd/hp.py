@@ -61,6 +61,7 @@ EXPORTS = ("lamsa_hp_para_init", "lamsa_hp_para_finish", "lamsa_hp_create", "lam
            "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve", "lamsa_hp_set_result_tags")
 
 TAG_MISMATCHES = 1      # LAMSA_HP_TAG_MISMATCHES: every record of the result stream also lists its mismatches
+TAG_EQX = 2             # LAMSA_HP_TAG_EQX: the CIGARs of the result stream are in =/X form (every M split into '=' 7 and 'X' 8 pieces)
 
 _lib = None
 
@@ -188,7 +189,9 @@ class LamsaHp:
 
     def set_result_tags(self, flags):
         """Optional items of the result streams of later batches (TAG_MISMATCHES: after its CIGAR words every record carries
-        n_mm and n_mm words ref_off << 2 | base); 0 = none, the default."""
+        n_mm and n_mm words ref_off << 2 | base; TAG_EQX: cigar_n and the CIGAR words of every record are the =/X form, each M
+        element split into its '=' (op 7) and 'X' (op 8) pieces, every other word unchanged; both may be set, the lists are in
+        the stream only with TAG_MISMATCHES); 0 = none, the default.  Raises while batches are in flight."""
         rc = self.L.lamsa_hp_set_result_tags(self._h, int(flags))
         if rc != 0:
             raise RuntimeError("lamsa_hp_set_result_tags failed: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
