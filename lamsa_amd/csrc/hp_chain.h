@@ -5,7 +5,7 @@
 //   dp_update_range    <- frag_dp_update        :701   targets in order; candidates = the target's neighbours in the
 //                                                      (contig, strand, position) order, spread over the 64 lanes
 //   min_extend_all <- frag_min_extend           :1031  all MIN hits x all hits, blocked, records in registers
-//   branch_track / cut_branch / best_son <- :873,:831,:808   (pointer chasing, wave-uniform)
+//   branch_track / cut_branch / best_son <- :873,:831,:808   (pointer chasing, wave-uniform; hp_track.h: through HBM, or on the LDS image of the largest cluster)
 //   reach_run      (no counterpart)             the hits that can be connected to an anchor at all: an exact run of the sorted order
 //   mini_line      <- frag_mini_dp_line         :1068  mini_line_regs / mini_line_sets: the whole pass on registers;
 //                                                      mini_line_mem: through memory, for passes with more than 256 listed hits
@@ -645,123 +645,11 @@ HP_FN int ns_add_bounded(NScore &ns, int node, int score, int NM)
     }
     return -2;
 }
-// path (may be null): the ancestors of `node` in lane order, n_path <= 64 of them, when the caller has just walked them -- they are
-// then marked with one store instead of being chased through n_from again
-HP_FN void ns_add_end(ReadCtx &r, NScore &ns, int score, int NM, int node, const wv::Lane<int> *path = nullptr, int n_path = 0)
-{   // node_add_score, lamsa_dp_con.c:786
-    if (score < ns.min_score_thd) return;
-    if (ns.node_n >= ns.cap) { r.cx.status |= ST_OVERFLOW; return; }
-    ns.score[ns.node_n] = score; ns.NM[ns.node_n] = NM; ns.node[ns.node_n++] = node;
-    r.nd[node].dp_flag = TRACKED_FLAG;
-    if (path) { HP_G NodeS *gd = (HP_G NodeS *)r.nd; WAVE_FOR(l) { if (l < n_path) gd[(*path)[l]].dp_flag = TRACKED_FLAG; } return; }
-    for (int t = r.n_from[node]; t >= 0; t = r.n_from[t]) r.nd[t].dp_flag = TRACKED_FLAG;
-}
-
-// ---------------------------------------------------------------- forest -> disjoint paths
-HP_FN int best_son(ReadCtx &r, int f)
-{   // get_max_son, :808
-    int max_score = 0, max_NM = 0, max_dis = 0, flag_thd = F_INIT, max = -1;
-    const int x = r.n_seed[f];
-    for (int s = r.n_first[f], c = 0; c < r.n_son_n[f] && s >= 0; s = r.n_next[s], ++c) {
-        const int mf = r.nd[s].match_flag, sx = r.n_seed[s];
-        if (mf <= flag_thd && (r.n_max_score[s] > max_score || (r.n_max_score[s] == max_score && (sx - x < max_dis || r.n_max_NM[s] < max_NM)))) {
-            max = s; max_score = r.n_max_score[s]; max_NM = r.n_max_NM[s]; max_dis = sx - x;
-            if (mf <= F_MATCH_THD) flag_thd = F_MATCH_THD;
-        }
-    }
-    return max;
-}
-HP_FN void detach(ReadCtx &r, int s, int max_node, NScore &ns)
-{   // :842-847 / :851-857 / :893-899
-    r.n_from[s] = -1;
-    r.n_max_score[s] -= (r.nd[s].score - 1);
-    r.n_max_NM[s] -= (r.nd[s].NM - r.h_nm[s]);
-    r.n_node_n[max_node] -= (r.n_node_n[s] - 1);
-    ns_add_end(r, ns, r.n_max_score[s], r.n_max_NM[s], max_node);
-}
-HP_INL void leaf_mark(ReadCtx &r, int f)
-{   // see track_leaves: the driver only visits seeds whose bit is set
-    if (r.leaf_on) { const int x = r.n_seed[f]; r.leaf_bits[x >> 5] |= (int)(1u << (x & 31)); }
-}
-HP_FN void cut_branch(ReadCtx &r, int f, NScore &ns)
-{   // :831-870
-    const int keep = best_son(r, f);
-    if (keep < 0) { r.cx.status |= ST_REFEXIT; r.n_in_de[f] = 0; leaf_mark(r, f); return; }
-    for (int s = r.n_first[f], c = 0, nn = r.n_son_n[f]; c < nn && s >= 0; ++c) {
-        const int nxt = r.n_next[s];
-        if (s != keep) detach(r, s, r.n_max_node[s], ns);
-        s = nxt;
-    }
-    if (r.nd[f].score > r.n_max_score[keep]) {        // negative edge
-        r.n_in_de[keep] = -1;
-        detach(r, keep, r.n_max_node[keep], ns);
-        r.n_son_n[f] = 0; r.n_first[f] = r.n_last[f] = -1;
-        r.n_max_node[f] = f; r.n_max_score[f] = r.nd[f].score; r.n_max_NM[f] = r.nd[f].NM;
-    } else {
-        r.n_son_n[f] = 1; r.n_first[f] = r.n_last[f] = keep; r.n_next[keep] = -1;
-        r.n_max_node[f] = r.n_max_node[keep]; r.n_max_score[f] = r.n_max_score[keep]; r.n_max_NM[f] = r.n_max_NM[keep];
-    }
-    r.n_in_de[f] = 0;
-    leaf_mark(r, f);                                  // f is complete: a track starts from it when its seed is reached
-}
-HP_HOT void branch_track(ReadCtx &r, int n, NScore &ns)
-{   // branch_track_new, :873-920
-    // The walk up a chain is a pointer chase through HBM: what a step needs (son count, score, predecessor) is requested together, one
-    // memory round trip per step, and the nodes walked are kept in a lane register so that node_add_score need not chase them again.
-    const HP_G int32_t *g_from = (const HP_G int32_t *)r.n_from, *g_son_n = (const HP_G int32_t *)r.n_son_n;
-    const HP_G NodeS *g_nd = (const HP_G NodeS *)r.nd;
-    HP_G int32_t *g_ms = (HP_G int32_t *)r.n_max_score, *g_mn = (HP_G int32_t *)r.n_max_NM, *g_mx = (HP_G int32_t *)r.n_max_node, *g_in_de = (HP_G int32_t *)r.n_in_de;
-    int max_score, max_NM, max_node;
-    g_in_de[n] = -1;
-    const int n_sons = g_son_n[n], n_score = g_nd[n].score, n_NM = g_nd[n].NM;
-    int fa = g_from[n];
-    if (n_sons == 0) { max_node = n; max_score = n_score; max_NM = n_NM; }      // (stored below, when and where they are read again)
-    else { max_node = g_mx[n]; max_score = g_ms[n]; max_NM = g_mn[n]; }
-    wv::Lane<int> path;                               // the ancestors of max_node walked so far, while path_ok
-    WAVE_FOR(l) { path[l] = 0; }
-    int n_path = 0; bool path_ok = n_sons == 0;       // a leaf: max_node is n itself, its ancestors are exactly the nodes walked below
-    // What the reference stores in every node it walks over (max_score, max_NM, max_node, in_de = -1; :885-910) is read again only for
-    // the node right below a node with several sons (get_max_son / cut_branch look at their sons) or below a negative edge: the walk
-    // keeps the three values in registers and stores them for that node alone -- four stores less per step.  in_de is only ever
-    // compared with 0 (is the node a leaf?), and a walked node with one son keeps its 1.
-    int prev = n;                                     // the node below fa
-    while (fa >= 0) {
-        const int fa_sons = g_son_n[fa], fa_score = g_nd[fa].score, fa_from = g_from[fa];
-#ifdef HP_PROF_TRACK
-        if (HP_PROF_CHAIN_ON && r.prof) r.prof[20] += 1;
-#endif
-        if (fa_sons == 1) {
-            if (fa_score > max_score) {               // negative edge
-                const int s = r.n_first[fa];
-                g_ms[prev] = max_score; g_mn[prev] = max_NM; g_mx[prev] = max_node;       // s == prev: detach reads them
-                wv::sync();
-                r.n_in_de[s] = -1;
-                detach(r, s, max_node, ns);
-                r.n_son_n[fa] = 0; r.n_first[fa] = r.n_last[fa] = -1;
-                max_score = r.nd[fa].score; max_NM = r.nd[fa].NM; max_node = fa;
-                n_path = 0; path_ok = true;           // from here on the ancestors of max_node = fa are what is walked next
-            } else if (path_ok) {
-                if (n_path < 64) { WAVE_FOR(l) { if (l == n_path) path[l] = fa; } ++n_path; } else path_ok = false;
-            }
-            prev = fa;
-            fa = fa_from;                             // detach() above changes n_from of the son only, never of fa
-        } else {
-            g_ms[prev] = max_score; g_mn[prev] = max_NM; g_mx[prev] = max_node;           // prev is a son of fa: what get_max_son / cut_branch read
-            const int left_ = g_in_de[fa] - 1;
-            g_in_de[fa] = left_;
-#ifdef HP_PROF_TRACK
-            if (HP_PROF_CHAIN_ON && r.prof) r.prof[21] += 1;
-            const long long tcb_ = wv::clock();
-#endif
-            if (left_ == 0) { wv::sync(); cut_branch(r, fa, ns); }
-#ifdef HP_PROF_TRACK
-            if (HP_PROF_CHAIN_ON && r.prof) r.prof[22] += wv::clock() - tcb_;
-#endif
-            return;
-        }
-    }
-    ns_add_end(r, ns, max_score, max_NM, max_node, path_ok ? &path : nullptr, n_path);
-}
+// ---------------------------------------------------------------- branch tracking: node_add_score, get_max_son, cut_branch, branch_track_new
+// (hp_track.h: one body for the node state in HBM and for the image of the largest cluster in LDS)
+}  // namespace hp
+#include "hp_track.h"
+namespace hp {
 
 // ---------------------------------------------------------------- which hits can matter for the chain into `node`
 // A predecessor that get_fseed_dis connects to a target lies on the target's contig and strand within R(target) bases
@@ -811,35 +699,47 @@ HP_NOINL RunR reach_run(ReadCtx &r, int node, long long Rcap)
 // over all hits of the range marks the seeds that hold a leaf now (a bit per seed in LDS); a hit becomes a leaf later only
 // through cut_branch, which marks its seed (always an earlier one than the track that completed it); the driver visits the
 // marked seeds only, last to first, with the same test as before.
-HP_INL void track_slot(ReadCtx &r, int h0, int h1, int dp_flag, bool skip_lone, NScore &ns)
+// img: the image of a resident cluster (hp_track.h).  The state of a resident hit is the image's, not its stale copy in HBM: the
+// leaf test reads it there, and the track of a resident leaf runs on the image.
+template <bool RES>
+HP_INL void track_slot(ReadCtx &r, int h0, int h1, int dp_flag, bool skip_lone, NScore &ns, const TrImg &img)
 {
+    const HP_G int32_t *g_rnk = (const HP_G int32_t *)r.rnk;
     const HP_G NodeS *ns_ = (const HP_G NodeS *)r.nd;
     const HP_G int32_t *g_in_de = (const HP_G int32_t *)r.n_in_de, *g_from = (const HP_G int32_t *)r.n_from, *g_son_n = (const HP_G int32_t *)r.n_son_n;
     for (int b = h0; b < h1; b += 64) {
-        wv::Lane<int> leaf;
+        wv::Lane<int> leaf, place;
         WAVE_FOR(l) {
             const int k = b + l;
-            int v = 0;
+            int v = 0, pl = -1;
             if (k < h1) {
-                int q[4]; hp_load16((const HP_G char *)(ns_ + k) + 16, q); v = (int)(int8_t)(q[1] & 0xff) == dp_flag && g_in_de[k] == 0;
-                // A hit without predecessor and without sons is a path of its own with score 1: node_add_score (:786) drops it when the
-                // threshold is above that, and nothing reads what branch_track_new would leave in its own fields
-                if (v && skip_lone && g_from[k] < 0 && g_son_n[k] == 0) v = 0;
+                if (RES && img.on) { const int p = g_rnk[k] - img.lo; if (p >= 0 && p < img.n) pl = p; }
+                if (pl >= 0) v = TrLds(r, img).leaf(pl, dp_flag, skip_lone);         // a resident hit: nothing of it is read from HBM
+                else {
+                    int q[4]; hp_load16((const HP_G char *)(ns_ + k) + 16, q); v = (int)(int8_t)(q[1] & 0xff) == dp_flag && g_in_de[k] == 0;
+                    // A hit without predecessor and without sons is a path of its own with score 1: node_add_score (:786) drops it when the
+                    // threshold is above that, and nothing reads what branch_track_new would leave in its own fields
+                    if (v && skip_lone && g_from[k] < 0 && g_son_n[k] == 0) v = 0;
+                }
             }
-            leaf[l] = v;
+            leaf[l] = v; place[l] = pl;
         }
         for (unsigned long long m = wv::ballot(leaf); m; m &= m - 1) {
 #ifdef HP_PROF_TRACK
             const long long tb_ = wv::clock();
 #endif
-            branch_track(r, b + __builtin_ctzll(m), ns);
+            const int q_ = __builtin_ctzll(m), pl = RES && img.on ? wv::bcast(place, q_) : -1;
+            if (RES && pl >= 0) { HP_STAT_ADD(50, 1); branch_track(TrLds(r, img), r, pl, ns); }
+            else { if (RES && img.on) HP_STAT_ADD(51, 1); branch_track(TrHbm(r), r, b + q_, ns); }
 #ifdef HP_PROF_TRACK
             if (HP_PROF_CHAIN_ON && r.prof) { r.prof[17] += wv::clock() - tb_; r.prof[18] += 1; }
 #endif
         }
     }
 }
-HP_NOINL void track_leaves(ReadCtx &r, int first_slot, int last_slot, int dp_flag, NScore &ns)
+// RES: the caller may have made a cluster resident (the first round only); without it the routine holds the HBM tracking alone
+template <bool RES>
+HP_INL void track_leaves_on(ReadCtx &r, int first_slot, int last_slot, int dp_flag, NScore &ns, const TrImg &img)
 {
     const HP_G NodeS *ns_ = (const HP_G NodeS *)r.nd;
     const HP_G int32_t *g_in_de = (const HP_G int32_t *)r.n_in_de, *g_from = (const HP_G int32_t *)r.n_from, *g_son_n = (const HP_G int32_t *)r.n_son_n;
@@ -850,7 +750,7 @@ HP_NOINL void track_leaves(ReadCtx &r, int first_slot, int last_slot, int dp_fla
     if (last_slot < first_slot) return;
     const int nw = (last_slot >> 5) + 1, w_lo = first_slot >> 5;
     if (nw > r.cx.lds_words) {                           // more seeds than this wave's LDS has bits for: every seed, as the reference
-        for (int i = last_slot; i >= first_slot; --i) track_slot(r, (int)(g_hoff[i] - hb), (int)(g_hoff[i + 1] - hb), dp_flag, skip_lone, ns);
+        for (int i = last_slot; i >= first_slot; --i) track_slot<RES>(r, (int)(g_hoff[i] - hb), (int)(g_hoff[i + 1] - hb), dp_flag, skip_lone, ns, img);
         return;
     }
 #ifdef HP_PROF_TRACK
@@ -893,10 +793,18 @@ HP_NOINL void track_leaves(ReadCtx &r, int first_slot, int last_slot, int dp_fla
 #ifdef HP_PROF_TRACK
             if (HP_PROF_CHAIN_ON && r.prof) r.prof[19] += 1;
 #endif
-            track_slot(r, (int)(g_hoff[i] - hb), (int)(g_hoff[i + 1] - hb), dp_flag, skip_lone, ns);
+            track_slot<RES>(r, (int)(g_hoff[i] - hb), (int)(g_hoff[i + 1] - hb), dp_flag, skip_lone, ns, img);
         }
     }
     r.leaf_on = false;
+}
+HP_NOINL void track_leaves(ReadCtx &r, int first_slot, int last_slot, int dp_flag, NScore &ns)
+{
+    track_leaves_on<false>(r, first_slot, last_slot, dp_flag, ns, TrImg{0, 0, 0, 0});
+}
+HP_NOINL void track_leaves_img(ReadCtx &r, int first_slot, int last_slot, int dp_flag, NScore &ns, TrImg img)
+{
+    track_leaves_on<true>(r, first_slot, last_slot, dp_flag, ns, img);
 }
 
 // ---------------------------------------------------------------- frag_mini_dp_line with the whole pass in registers
@@ -1801,7 +1709,23 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
     NScore &ns = loc->ns;
     if (!ns_alloc(r.cx, ns, H + 1, 0)) return false;
     ns.min_score_thd = 2;
-    track_leaves(r, 0, seed_out - 1, MIN_FLAG, ns);                                                 // :1356-1361
+    // the read's largest cluster in LDS while its tracks run (hp_track.h); an image that is off leaves everything in HBM
+#ifdef HP_PROF_TRACK
+    const long long ti0_ = wv::clock();
+#endif
+    const TrImg img = have_cl && seed_out > 1 ? track_image_build(r, C.cs, C.n_cl, seed_out - 1) : TrImg{0, 0, 0, 0};
+#ifdef HP_PROF_TRACK
+    if (HP_PROF_CHAIN_ON && r.prof) r.prof[16] += wv::clock() - ti0_;         // the image's build and write-back count with the marking pass
+#endif
+    if (img.on && all_min) HP_STAT_ADD(63, 1);
+    track_leaves_img(r, 0, seed_out - 1, MIN_FLAG, ns, img);                                             // :1356-1361
+#ifdef HP_PROF_TRACK
+    const long long ti1_ = wv::clock();
+#endif
+    if (img.on) track_image_store(r, img);
+#ifdef HP_PROF_TRACK
+    if (HP_PROF_CHAIN_ON && r.prof) r.prof[16] += wv::clock() - ti1_;
+#endif
 
     HP_CSTAMP(8);
 #if defined(HP_CHAIN_STOP) && HP_CHAIN_STOP == 3

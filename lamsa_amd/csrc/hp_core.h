@@ -79,7 +79,13 @@ struct Ctx {
 //  32 clusters chained out of LDS (dp_cluster_lds), 33 clusters sent through HBM, 34 clusters handled one per lane (cluster_lane), 35 / 36 line sets staged in LDS / left in
 //  HBM (lset_stage), 37 / 38 sorts in one LDS block / in several (hp_sort.h), 39 gaps of the scan by seed range handed to a lane (gap_lane);
 //  largest values: 40 cluster chained out of LDS, 41 cluster sent through HBM, 42 hits listed for a wave-wide gap, 43 survivors of a gap a lane took,
-//  44 lines handed to lset_stage, 45 / 46 gaps of a line scanned by seed range / by cluster, 47 cluster handled by a lane, 48 clusters of a read
+//  44 lines handed to lset_stage, 45 / 46 gaps of a line scanned by seed range / by cluster, 47 cluster handled by a lane, 48 clusters of a read;
+//  branch tracking with the largest cluster in LDS (hp_track.h): 49 reads with a resident cluster, 50 tracks on the image, 51 tracks through HBM while
+//  an image is resident, 52 walk steps on the image, 53 cut_branch on the image with two or more sons, 54 / 55 negative edges detached on the image in
+//  the walk / in cut_branch, 56 end nodes on the image whose chain of more than 64 nodes is marked by the chase through `from`,
+//  58 / 59 get_max_son on the image: a son that ties the best on max_score at another seed distance / at the same one (max_NM decides), 60 a son skipped for its edge
+//  class once a match-class son is held, 61 largest clusters refused by the packing checks, 62 cut_branch on the image with three or more sons, 63 reads with a resident cluster whose first pass
+//  takes every hit (all_min); largest value: 57 resident cluster
 #ifndef HP_DPLOG
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { } while (0)      // tests' CPU build: one record per DP call (tools/dp_shapes.py)
 #endif
