@@ -162,7 +162,22 @@ typedef struct lamsa_hp_batch {
  * pieces -- the maximal runs of aligned bases that equal the reference ('=') or differ from it ('X'; a read N differs).
  * The pieces are in order, none is empty, neighbours alternate; every other element is copied as it is, and pieces never
  * merge across elements ("..1X 2I 1X.." stays three elements).  So the X lengths of a record sum to its n_mm, the pieces
- * of one element with 7/8 read as 0 add up to the original word, and a record has at most cigar_n + 2 n_mm words. */
+ * of one element with 7/8 read as 0 add up to the original word, and a record has at most cigar_n + 2 n_mm words.
+ * With LAMSA_HP_TAG_LEFT_ALIGN set, the gaps of every record are left-aligned before anything is counted.  The definition
+ * is this procedure on one record: op[0..n), len[0..n) its CIGAR in M form; R the read on the record's strand (as SEQ is
+ * printed, soft clips included), compared by base code 0-4, so N equals N; T the forward reference from the record's
+ * offset, compared by .pac code:
+ *     for i = 0 .. n-1, ascending:
+ *         if op[i] in {I, D} and 0 < i < n-1 and op[i-1] == M and op[i+1] == M:
+ *             k = len[i]; q = read position of element i; p = reference position of element i
+ *             while len[i-1] > 1 and ( op[i] == D ? T[p-1] == T[p+k-1] : R[q-1] == R[q+k-1] ):
+ *                 len[i-1] -= 1; len[i+1] += 1; p -= 1; q -= 1
+ * Only M lengths change: the element count, the order of the ops, the clips, the offset, the read and reference spans,
+ * NM, AS, the line totals and the number of mismatches are what they were, and a second application changes nothing.
+ * A gap never consumes the M before it, so it never merges with or crosses another gap or a clip and never reaches the
+ * record's start; a gap that touches another gap or a clip stays and stops its neighbours.  A mismatch inside a stretch
+ * that a deletion of k bases moved across keeps its base and gets ref_off + k.  Gaps are not right-aligned or merged, and
+ * where the records of a line meet is not touched.  The mismatch lists and the =/X form describe the shifted alignment. */
 typedef struct lamsa_hp_result {
     const int32_t *stream; int64_t stream_words;
     const int64_t *read_off;      /* [n_reads] start of read r's stream */
@@ -179,9 +194,12 @@ int lamsa_hp_align_batch(lamsa_hp_handle *h, const lamsa_hp_batch *batch, lamsa_
  * stream as documented without them.  LAMSA_HP_TAG_MISMATCHES: every record also lists its mismatches (what a SAM
  * writer needs for MD:Z without reading the reference again).  LAMSA_HP_TAG_EQX: the CIGARs are in =/X form (the
  * device splits the M elements by the same lists, which are in the stream only if LAMSA_HP_TAG_MISMATCHES is set too).
- * flags outside LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX: LAMSA_HP_EINVAL; so while a batch or run is in flight. */
+ * LAMSA_HP_TAG_LEFT_ALIGN: the gaps of every CIGAR are left-aligned (the device shifts them before it counts; no word
+ * is added).  The items combine freely.  Flags outside the three (4 among them): LAMSA_HP_EINVAL; so while a batch or
+ * run is in flight. */
 #define LAMSA_HP_TAG_MISMATCHES 1
 #define LAMSA_HP_TAG_EQX 2
+#define LAMSA_HP_TAG_LEFT_ALIGN 8
 int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags);
 
 /* The same in two steps, so that a caller can keep a batch resident in HBM and overlap or

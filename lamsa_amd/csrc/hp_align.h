@@ -109,9 +109,11 @@ HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
     }
 }
 
-// The mismatch lists of a line (LineRes::ev, made under any LAMSA_HP_TAG_* item) -- at most one per aligned read base, the records of a
+// The mismatch lists of a line (LineRes::ev, made under either item of HP_TAGS_LISTS) -- at most one per aligned read base, the records of a
 // line cover disjoint parts of the read -- and what the items add to the line's result words: LAMSA_HP_TAG_MISMATCHES the lists and a
 // count per record, LAMSA_HP_TAG_EQX at most two words per mismatch (a record has at most cigar_n + 2 n_mm words, hp_eqx.h)
+// LAMSA_HP_TAG_LEFT_ALIGN adds no word and needs no list.
+enum { HP_TAGS_LISTS = LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX };
 HP_INL int line_ev_cap(int L) { return L + 64; }
 HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
 HP_INL int line_eqx_words(int L) { return 2 * (L + 64); }
@@ -128,9 +130,10 @@ HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int re
     LineRes *la = (LineRes *)arena_alloc(cx, sizeof(LineRes));
     cig_t *cur_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)cur_cap);
     cig_t *rec_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)(cur_cap + 4 * HP_REC_MAX));
-    const int ev_cap = tags ? line_ev_cap(r.L) * scale : 0;
-    int32_t *ev = tags ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)ev_cap) : nullptr;
-    if (!la || !cur_buf || !rec_buf || (tags && !ev)) { arena_release(cx.tmp, mark); return; }
+    const bool lists = (tags & HP_TAGS_LISTS) != 0;
+    const int ev_cap = lists ? line_ev_cap(r.L) * scale : 0;
+    int32_t *ev = lists ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)ev_cap) : nullptr;
+    if (!la || !cur_buf || !rec_buf || (lists && !ev)) { arena_release(cx.tmp, mark); return; }
     la->ev = ev; la->ev_cap = ev_cap; la->tags = tags;
     for (int j = 0; j < F.n; ++j) {
         if (!fill_line(r, F, j, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX)) break;
@@ -242,7 +245,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
     if (skip) { cx.status |= ST_UNSUPPORTED; r.H = 0; r.seed_out = 0; }
     const int H = r.H;
     // read-lifetime allocations
-    const int tags = a.in.tags & (LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX);
+    const int tags = a.in.tags & (HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN);
     const int out_cap = (int)read_out_cap(r.L, a.scale, tags);
     OutBuf o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);

@@ -342,10 +342,10 @@ static int grow(lamsa_hp_handle *h, DevBuf &b, size_t bytes)
 
 // result + CIGAR bytes per read base of a wave's scratch; `eqx`: what the =/X words of LAMSA_HP_TAG_EQX add (a line's: 2 words per base,
 // line_eqx_words; a read's on the one-kernel path: 8, read_out_cap)
-static size_t tag_slab_per_base(int tags, int eqx) { return (size_t)(tags ? 152 : 128) + ((tags & LAMSA_HP_TAG_EQX) ? (size_t)eqx : 0); }
+static size_t tag_slab_per_base(int tags, int eqx) { return (size_t)((tags & HP_TAGS_LISTS) ? 152 : 128) + ((tags & LAMSA_HP_TAG_EQX) ? (size_t)eqx : 0); }
 static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale, int tags)
 {   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base; 24 more with the
-    // mismatch lists of any LAMSA_HP_TAG_* item, 40 more for the =/X words of LAMSA_HP_TAG_EQX: read_out_cap), and the direction matrix
+    // mismatch lists of LAMSA_HP_TAG_MISMATCHES or LAMSA_HP_TAG_EQX, 40 more for the =/X words of LAMSA_HP_TAG_EQX: read_out_cap), and the direction matrix
     // of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
     // Reads that need more flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
     const size_t z = (2 * (size_t)P.band_w + 128) * ((size_t)L + 256);
@@ -977,7 +977,7 @@ extern "C" int lamsa_hp_set_scratch_limit(lamsa_hp_handle *h, size_t bytes)
 
 extern "C" int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags)
 {
-    if (!h || (flags & ~(LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX))) return LAMSA_HP_EINVAL;
+    if (!h || (flags & ~(LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX | LAMSA_HP_TAG_LEFT_ALIGN))) return LAMSA_HP_EINVAL;
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight: collect them first"; return LAMSA_HP_EINVAL; }
     h->result_tags = flags;

@@ -44,6 +44,8 @@ struct BatchIn {
 //              [in.tags & LAMSA_HP_TAG_MISMATCHES] n_mm, n_mm words ref_off << 2 | base (res_aux, hp_fill.h)
 //              [in.tags & LAMSA_HP_TAG_EQX] cigar_n and the cigar words are the =/X form: every M split into its '=' (7) and 'X' (8) pieces
 //              by eqx_words (hp_eqx.h) from the same lists, which are shipped only under LAMSA_HP_TAG_MISMATCHES
+//              [in.tags & LAMSA_HP_TAG_LEFT_ALIGN] the gaps of every CIGAR are left-aligned (lalign_cigar, hp_lalign.h, called by res_aux before
+//              it counts): some M lengths differ, and with them the offsets of the lists and the =/X pieces; no word is added or dropped
 struct BatchOut {
     int32_t *stream;             // global result arena
     int64_t stream_cap;          // words

@@ -18,6 +18,7 @@
 // ST_REFEXIT and abandoned.
 #pragma once
 #include "hp_split.h"
+#include "hp_lalign.h"
 
 namespace hp {
 
@@ -29,8 +30,8 @@ struct Rec {                     // res_t, frag_check.h:46-59
 };
 struct LineRes {                 // line_aln_res, frag_check.h:61-73
     int line_score, tol_score, tol_NM, cur_res_n;
-    int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (any LAMSA_HP_TAG_* item needs them), or nullptr
-    int tags;                    // set by the caller: the LAMSA_HP_TAG_* items out_line writes (lists shipped / CIGARs in =/X form)
+    int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (LAMSA_HP_TAG_MISMATCHES and LAMSA_HP_TAG_EQX need them), or nullptr
+    int tags;                    // set by the caller: the LAMSA_HP_TAG_* items out_line writes (lists shipped / CIGARs in =/X form) and res_aux applies (gaps left-aligned)
     Rec rec[HP_REC_MAX];
 };
 
@@ -1038,6 +1039,9 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
         int32_t ref_len = cig_reflen(rec.cig.c, rec.cig.n);
         uint8_t *ref = (uint8_t *)arena_alloc(cx, (size_t)(ref_len > 0 ? ref_len : 0) + 16);
         if (!ref || !ref_fetch(r, rec.chr, rec.offset - 1, &ref_len, ref)) { arena_release(cx.tmp, mark); return false; }
+        // LAMSA_HP_TAG_LEFT_ALIGN: the gaps move first, in a pass of its own over the whole record (the M in front of a gap may lie in the block
+        // before it), so NM, AS, the lists and the =/X words below are those of the normalised CIGAR; lengths, clips and spans stay
+        if (la.tags & LAMSA_HP_TAG_LEFT_ALIGN) lalign_cigar(rec.cig.c, rec.cig.n, r.cur_read, r.L, ref, ref_len);
         int ref_i = 0, read_i = 0, n_mm = 0, n_m = 0, n_io = 0, n_ie = 0, n_do = 0, n_de = 0;
         bool bad = false;
         // 64 CIGAR elements at a time, one per lane: where each starts on the read and on the reference is a prefix sum

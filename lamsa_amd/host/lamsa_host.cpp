@@ -624,6 +624,43 @@ static void host_mismatches(ReadResult &R, const uint8_t *bseq, int read_len, co
             }
 }
 
+void rec_left_align(Rec &r, const uint8_t *rd, int read_len, const Index &ix)
+{
+    // the procedure of include/lamsa_hp.h (LAMSA_HP_TAG_LEFT_ALIGN) as it is written there, on the M form
+    std::vector<int32_t> &c = r.cigar;
+    const int n = (int)c.size();
+    if (n < 3 || r.chr < 1 || (size_t)r.chr > ix.len.size() || r.offset < 1) return;
+    int64_t read_tot = 0, ref_tot = 0;
+    for (int32_t w : c) { const int op = w & 0xf, len = w >> 4; if (len < 0) return; if (op == 0 || op == 1 || op == 4) read_tot += len; if (op == 0 || op == 2) ref_tot += len; }
+    if (read_tot > read_len || r.offset - 1 + ref_tot > ix.len[(size_t)r.chr - 1]) return;       // (a record that fits neither the read nor the contig is flagged elsewhere)
+    const int64_t k0 = ix.off[(size_t)r.chr - 1] + r.offset - 1;
+    auto T = [&](int64_t p) { const int64_t k = k0 + p; return (int)(ix.pac[(size_t)(k >> 2)] >> ((~k & 3) << 1) & 3); };
+    int64_t q = 0, p = 0;
+    for (int i = 0; i < n; ++i) {
+        const int op = c[(size_t)i] & 0xf, k = c[(size_t)i] >> 4;
+        if ((op == 1 || op == 2) && i > 0 && i < n - 1 && (c[(size_t)i - 1] & 0xf) == 0 && (c[(size_t)i + 1] & 0xf) == 0) {
+            while ((c[(size_t)i - 1] >> 4) > 1 && (op == 2 ? T(p - 1) == T(p + k - 1) : rd[q - 1] == rd[q + k - 1])) {
+                c[(size_t)i - 1] -= 1 << 4; c[(size_t)i + 1] += 1 << 4; --p; --q;
+            }
+        }
+        if (op == 0 || op == 1 || op == 4) q += k;
+        if (op == 0 || op == 2) p += k;
+    }
+}
+
+// rec_left_align on the records of rounds 1 and 2, each with the read on its own strand, for a library without lamsa_hp_set_result_tags
+// (the stage-4 records are shifted where they are made: rescue_finish)
+static void reads_left_align(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix)
+{
+    std::vector<uint8_t> rc;
+    for (int st = 0; st < 2; ++st)
+        for (Line &ln : R.stage[st])
+            for (Rec &r : ln.rec) {
+                if (r.nstrand == 0 && rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
+                rec_left_align(r, r.nstrand ? bseq : rc.data(), read_len, ix);
+            }
+}
+
 void rec_to_eqx(Rec &r)
 {
     std::vector<int32_t> out;
@@ -1144,12 +1181,14 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     if (rc != LAMSA_HP_OK) for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh);
     const int G = (int)std::max<size_t>(1, hs.size());
     if (rc != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] no usable MI355X / HIP device (lamsa_hp_create: %d); this build has no CPU path\n", rc); return 2; }
-    // --MD, --cs: every handle lists the mismatches of its records in the result stream; --eqx: it writes the CIGARs in =/X form.  Against
-    // a library without lamsa_hp_set_result_tags the host makes the lists (host_mismatches) and the =/X form (rec_to_eqx) itself.
+    // --MD, --cs: every handle lists the mismatches of its records in the result stream; --eqx: it writes the CIGARs in =/X form;
+    // --left-align: it shifts the gaps before it counts.  Against a library without lamsa_hp_set_result_tags the host shifts the gaps
+    // (rec_left_align) and makes the lists (host_mismatches) and the =/X form (rec_to_eqx) itself, in that order.
     const bool need_mm = opt.tag_md || opt.tag_cs;
-    const int dev_tags = lamsa_hp_set_result_tags != nullptr ? (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) : 0;
+    const int dev_tags = lamsa_hp_set_result_tags != nullptr ? (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) | (opt.left_align ? LAMSA_HP_TAG_LEFT_ALIGN : 0) : 0;
     const bool dev_mm = (dev_tags & LAMSA_HP_TAG_MISMATCHES) != 0;
     const bool host_mm = (need_mm || opt.tag_eqx) && lamsa_hp_set_result_tags == nullptr, host_eqx = opt.tag_eqx && !(dev_tags & LAMSA_HP_TAG_EQX);
+    const bool host_la = opt.left_align && !(dev_tags & LAMSA_HP_TAG_LEFT_ALIGN);           // --left-align without the device item: rec_left_align, before the lists and the =/X form
     for (lamsa_hp_handle *hh : hs) {
         if (!dev_tags) break;
         const int e = lamsa_hp_set_result_tags(hh, dev_tags);
@@ -1389,6 +1428,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
                 parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm);
+                if (host_la && R.status == 0) reads_left_align(R, codes + roff[r], L, ix);
                 if (host_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
                 if (host_eqx && R.status == 0) for (int st = 0; st < 2; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) rec_to_eqx(x);
                 if (rescue && R.status == 0) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
@@ -1430,7 +1470,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
                 if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) {
-                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp);
+                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp, opt.left_align != 0);      // stage-4 records: always shifted on the host, before their rec_aux
                     if (opt.tag_eqx) for (Line &ln : R.stage[2]) for (Rec &x : ln.rec) rec_to_eqx(x);       // stage-4 records are made on the host, with their lists (rec_aux)
                 }
                 if (R.status != 0) {

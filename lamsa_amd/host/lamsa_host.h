@@ -75,6 +75,10 @@ void rank_results(ReadResult &R, int read_len, const lamsa_hp_para &P);
 // the record's CIGAR into =/X form from its mismatch list, to the definition of include/lamsa_hp.h (what the device does under
 // LAMSA_HP_TAG_EQX): for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host
 void rec_to_eqx(Rec &r);
+// the gaps of the record's CIGAR (M form) left-aligned, by the procedure of include/lamsa_hp.h (what the device does under
+// LAMSA_HP_TAG_LEFT_ALIGN): for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host.
+// oriented_read: the read's base codes on the record's strand (reverse complement for '-'), read_len of them
+void rec_left_align(Rec &r, const uint8_t *oriented_read, int read_len, const Index &ix);
 
 // a path as one word of a POSIX shell command line: wrapped in single quotes, embedded ones spelled '\''
 inline std::string shell_quote(const std::string &p) { std::string o = "'"; for (char c : p) { if (c == '\'') o += "'\\''"; else o += c; } return o + "'"; }
@@ -94,6 +98,7 @@ struct Options {
     int parse_only = 0;                                   // --parse-only: read and parse the inputs, no GPU work, no output (ingest timing)
     int tag_md = 0, tag_sa = 0;                           // --MD, --SA: MD:Z / SA:Z at the end of every mapped record (not in the reference's output)
     int tag_eqx = 0, tag_cs = 0;                          // --eqx: every printed CIGAR in =/X form (LAMSA_HP_TAG_EQX, include/lamsa_hp.h); --cs: cs:Z (short form) on every mapped record
+    int left_align = 0;                                   // --left-align: the gaps of every printed CIGAR shifted as far left as they go (LAMSA_HP_TAG_LEFT_ALIGN, include/lamsa_hp.h)
     float ed_rate = -1, mis_rate = -1, mat_rate = -1;     // -e, -x; defaults per read type (src/lamsa_aln.h:26-70)
     std::string gem_dir;                                  // directory holding gem-mapper (default: <directory of this binary>/gem)
     int chunk_reads = 16384; int64_t chunk_bases = 256ll << 20;     // reads per GPU batch (the reference's CHUNK_READ_N is 128 per thread pool)

@@ -34,6 +34,8 @@ static int usage()
                     "         --eqx (every CIGAR -- field 6, inside XA:Z and SA:Z -- in =/X form: each M split into runs that equal the reference, '=', or differ, 'X';\n"
                     "         the GPU splits them as it writes the records),\n"
                     "         --cs (cs:Z tag, short form: :n identical bases, *xy reference base x read as y, +seq inserted, -seq deleted; lowercase, forward strand).\n"
+                    "         --left-align (every gap with aligned bases on either side shifted as far left as it goes without changing score or NM -- field 6,\n"
+                    "         XA:Z and SA:Z; MD, cs and =/X describe the shifted alignment; the GPU shifts them before it counts the mismatches).\n"
                     "         The tags follow NM, AS and XA in the order MD, cs, SA; none of this is in the reference's output\n\n");
     return 1;
 }
@@ -65,7 +67,7 @@ int main(int argc, char *argv[])
         {"max-skel",1,0,'s'},{"max-reg",1,0,'R'},{"bwt-kmer",1,0,'k'},{"fastest",0,0,'f'},{"ed-rate",1,0,'e'},{"diff-rate",1,0,'d'},
         {"mis-rate",1,0,'x'},{"read-type",1,0,'T'},{"match-sc",1,0,'m'},{"mis-pen",1,0,'M'},{"open-pen",1,0,'O'},{"ext-pen",1,0,'E'},
         {"band-width",1,0,'w'},{"end-bonus",1,0,'b'},{"max-out",1,0,'r'},{"gap-split",1,0,'g'},{"soft-clip",0,0,'S'},{"comment",0,0,'C'},
-        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{0,0,0,0}};
+        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{"left-align",0,0,1014},{0,0,0,0}};
     optind = 2;
     while ((c = getopt_long(argc, argv, "t:l:i:p:V:v:s:R:k:fm:M:O:E:w:b:e:d:x:T:r:g:SCo:hHNI", lopt, NULL)) >= 0) {
         switch (c) {
@@ -117,6 +119,7 @@ int main(int argc, char *argv[])
             case 1011: opt.tag_sa = 1; break;
             case 1012: opt.tag_eqx = 1; break;
             case 1013: opt.tag_cs = 1; break;
+            case 1014: opt.left_align = 1; break;
             case 1007: { opt.devices.clear(); for (const char *q = optarg; *q;) { opt.devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; } break; }
         case 1001: opt.seed_result = optarg; break;
         case 1002: opt.chunk_reads = atoi(optarg) > 0 ? atoi(optarg) : opt.chunk_reads; break;

@@ -413,7 +413,7 @@ bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts
     return ok && read_i == read_len && ref_i == ref_len;
 }
 
-void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp)
+void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, bool left_align)
 {
     std::vector<Line> &out = R.stage[2];
     out.clear();
@@ -448,6 +448,7 @@ void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index
             if (rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
             rd = rc.data();
         }
+        if (left_align) rec_left_align(r, rd, read_len, ix);           // --left-align: before anything is counted or listed, as on the device
         AuxCounts k;
         if (!rec_aux(ix, rd, read_len, r, k)) { R.status |= LAMSA_HP_ST_REFEXIT; return; }      // the reference exits with "Unmatched length"
         r.NM = k.n_mm + k.n_ie + k.n_de;

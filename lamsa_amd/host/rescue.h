@@ -59,7 +59,7 @@ struct DpResults { const int32_t *score, *qle, *tle; const int64_t *cig_off; con
 struct AuxCounts { int n_mm = 0, n_m = 0, n_io = 0, n_ie = 0, n_do = 0, n_de = 0; };
 bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts &k);
 
-// finish: DP results -> R.stage[2]
-void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp);
+// finish: DP results -> R.stage[2]; left_align: the gaps of every record are left-aligned (rec_left_align) before rec_aux walks it
+void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, bool left_align = false);
 
 }  // namespace lamsa
