@@ -513,8 +513,13 @@ static void prof_report(Slot &T, const long long *d_prof, int n)
         fprintf(stderr, "[HP_PROF] branch tracking (-DHP_PROF_TRACK: the line_build stamps below are off): marking pass, image build and write-back %lld Mcyc; %lld seeds visited; %lld tracks, %lld Mcyc in them, %lld steps up; "
                         "%lld arrivals at a node with several sons, %lld Mcyc in cut_branch\n", sum[16] / 1000000, sum[19], sum[18], sum[17] / 1000000, sum[20], sum[21], sum[22] / 1000000);
 #endif
+#ifdef HP_PROF_EDGE
+        fprintf(stderr, "[HP_PROF] main pass (-DHP_PROF_EDGE: the line_build stamps below are off), Mcyc: dp_cluster_lds load+pack %lld, MIN extension %lld, target loop %lld, write-back %lld; cluster_lane %lld; build_sons %lld\n",
+                sum[16] / 1000000, sum[17] / 1000000, sum[18] / 1000000, sum[19] / 1000000, sum[20] / 1000000, sum[21] / 1000000);
+#else
         fprintf(stderr, "[HP_PROF] line_build: %lld lines (%lld without a gap), %lld anchors, %lld gaps | Mcyc: anchor walk %lld, gap list %lld, gaps in lanes %lld, gaps one by one %lld, assembly %lld\n",
                 sum[21], sum[22], sum[12], sum[23], sum[16] / 1000000, sum[17] / 1000000, sum[18] / 1000000, sum[19] / 1000000, sum[20] / 1000000);
+#endif
         fprintf(stderr, "[HP_PROF] gaps: %lld in lines with fewer than HP_GAP_MIN gaps (%lld lines with gaps); lane gaps: %lld hits scanned, %lld refused (range too long or too many active hits)\n", sum[54], sum[55], sum[11], sum[13]);
         { const char *nm[] = {"ksw_global", "ksw_extend", "backtrack", "ref_fetch", "head_fix", "frag_extend", "split_mapping", "tail_fix", "res_split", "res_aux", "mini_line_regs", "sort index"};
           for (int k = 0; k < 12; ++k) fprintf(stderr, "[HP_PROF] %-16s %8lld Mcyc %10lld calls\n", nm[k], sum[24 + 2 * k] / 1000000, sum[25 + 2 * k]);

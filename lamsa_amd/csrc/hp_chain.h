@@ -123,6 +123,56 @@ HP_INL EdgeK edge_consts(const lamsa_hp_para *P)
     k.mis3 = 3 * P->mismatch_thd; k.sv_len = P->SV_len_thd; k.half_split = P->split_len / 2;
     return k;
 }
+// a * k for two factors inside 24 signed bits, k wave-uniform (a constant of the handle): v_mul_i32_i24 instead of the 32-bit v_mul_lo_u32,
+// which to our knowledge issues at a quarter of the rate (an assumption: profiles/edge_diag_ab.txt).  The compiler cannot know the ranges of a
+// handle's constants, and HIP's __mul24 comes out as v_mul_lo_u32 here.  k is handed over in a scalar register.  The only device-only lines of the diagonal form below; edge_k24 says whether a handle's constants may go through it.
+HP_INL int mul24(int a, int k)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int p;
+    asm("v_mul_i32_i24 %0, %1, %2" : "=v"(p) : "s"(__builtin_amdgcn_readfirstlane(k)), "v"(a));
+    return p;
+#else
+    return a * k;
+#endif
+}
+// the constants in scalar registers (a routine that reads them through the read context holds them per lane otherwise)
+HP_INL EdgeK edge_uni(EdgeK k)
+{
+    k.seed_step = wv::uni(k.seed_step); k.seed_len = wv::uni(k.seed_len); k.match_dis = wv::uni(k.match_dis); k.high_err = wv::uni(k.high_err);
+    k.mis3 = wv::uni(k.mis3); k.sv_len = wv::uni(k.sv_len); k.half_split = wv::uni(k.half_split);
+    return k;
+}
+HP_INL bool edge_k24(const EdgeK &k) { return k.seed_step >= 0 && k.seed_step <= 0x7fffff && k.match_dis >= 0 && k.match_dis <= 0x7fffff; }
+
+// ---- the edge class in diagonal form, for two hits of ONE contig and strand.  With q the hit of the earlier seed and t the other,
+// get_fseed_dis (:607-619) is   dis = sp * (pos_t - pos_q) - (sid_t - sid_q) * seed_step - ld  =  D_t - D_q - ld,   ld = sp > 0 ? ld_q : ld_t,
+// where D_h = sp * pos_h - sid_h * seed_step is a constant of the hit, its diagonal (positions relative to any common base, seed ids likewise).
+// What is left of the span, `span >= seed_len` and the insert bound -(span - seed_len), and mat_dis = match_dis * dsid are products of |dsid| <= 32 767
+// with a constant of the handle: 24-bit multiplies.  (EdgeK gains no field for this: a wider EdgeK costs lines_pop 16 bytes of frame per lane.)
+HP_INL int hit_diag(const EdgeK &k, int sp, int rel, int sid) { return (int)((unsigned)(sp > 0 ? rel : 0 - rel) - (unsigned)mul24(sid, k.seed_step)); }
+HP_INL int edge_dis(int d_q, int d_t, int ld) { return (int)((unsigned)d_t - (unsigned)d_q - (unsigned)ld); }
+// M24: the products through mul24.  The lane routines (gap_edge, hp_cluster.h) keep the 32-bit multiplies: with the inline assembly of mul24
+// lines_pop, which holds them all, grows by 16 bytes of frame per lane, and written as a product of sign-extended 24-bit factors the compiler
+// still emits v_mul_lo_u32 wherever the constant sits in a scalar register (profiles/edge_diag_ab.txt).
+template <bool M24> HP_INL int edge_mul(int a, int k) { return M24 ? mul24(a, k) : a * k; }
+template <bool M24 = true>
+HP_INL int edge_class_diag(const EdgeK &k, int dis, int dsid)
+{
+    const int span = edge_mul<M24>(dsid, k.seed_step);
+    if (span < k.seed_len) return F_UNCONNECT;
+    const int mat_dis = edge_mul<M24>(dsid, k.high_err ? k.match_dis : 0) + (k.high_err ? 0 : k.match_dis);
+    if (dis <= mat_dis && dis >= -mat_dis) return dsid == 1 ? F_MATCH : (dsid <= k.mis3 ? F_MISMATCH : F_LONG_MISMATCH);
+    if (dis > mat_dis && dis < k.sv_len) return F_DELETE;
+    if ((dis < -mat_dis && dis >= k.seed_len - span) || (dis < -k.half_split && dis >= -k.sv_len)) return F_INSERT;
+    return F_UNCONNECT;
+}
+// the match classes alone (frag_min_extend, :1031-1066)
+HP_INL bool edge_match_diag(const EdgeK &k, int dis, int dsid)
+{
+    const int mat_dis = mul24(dsid, k.high_err ? k.match_dis : 0) + (k.high_err ? 0 : k.match_dis);
+    return mul24(dsid, k.seed_step) >= k.seed_len && dis <= mat_dis && dis >= -mat_dis;
+}
 HP_INL int edge_flag_packed(const EdgeK &k, const NodeS &pre, const NodeS &cur)
 {
     if ((pre.slot_j >> 14) == (cur.slot_j >> 14)) return F_UNCONNECT;
@@ -1681,8 +1731,14 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
                 if (geo32 && HP_CL_CAP_RT(1 << 20) >= HP_CLL_MCAP) {                                   // clusters of two to six hits: one per lane
                     const EdgeK K = edge_consts(P);
                     wv::sync();
+#ifdef HP_PROF_EDGE
+                    const long long tl0_ = wv::clock();
+#endif
                     WAVE_FOR(l) { const int n = csn[l] - csl[l]; if (l < cn && n >= 2 && n <= HP_CLL_MCAP) { HP_STAT_ADD(34, 1); HP_STAT_MAX(47, n); cluster_lane(r, K, C, r.cx.lds + l, csl[l], n, do_me); } }
                     wv::sync();
+#ifdef HP_PROF_EDGE
+                    if (r.prof) r.prof[20] += wv::clock() - tl0_;
+#endif
                 }
                 for (int q = 0; q < cn; ++q) {
                     const int lo = wv::bcast(csl, q), n = wv::bcast(csl, q + 1) - lo;
@@ -1699,7 +1755,13 @@ HP_NOINL bool chain_first(ReadCtx &r, FLines &F, FlStore *fs = nullptr)
             if (any_big) dp_update_range(r, hoff(r, 1), H, 0, MIN_FLAG, false, false, C.big);
         }
         if (!have_cl) arena_release(r.cx.tmp, cmark);                  // the clusters stay: the line loop below works on them (hp_gaps.h)
+#ifdef HP_PROF_EDGE
+        const long long ts0_ = wv::clock();
+#endif
         if (!build_sons(r, (HP_L uint64_t *)r.cx.lds, r.cx.lds_words / 2)) return false;
+#ifdef HP_PROF_EDGE
+        if (r.prof) r.prof[21] += wv::clock() - ts0_;
+#endif
     }
 
     HP_CSTAMP(7);

@@ -233,15 +233,11 @@ HP_NOINL void min_extend_clusters(ReadCtx &r, const Clusters &C, int p_lo, int p
 // and runs frag_dp_update (:701-764) over them exactly as dp_cluster_lds does.
 #define HP_CLL_MCAP (HP_LANE_STRIP_WORDS / 384 < 6 ? HP_LANE_STRIP_WORDS / 384 : 6)
 HP_INL int gap_edge(const EdgeK &K, int sp, int qpos, int qsid, int qld, int tpos, int tsid, int tld)
-{   // get_fseed_dis (:596-634) for two hits of the same contig and strand, the first of an earlier seed (cf. dp_cluster_lds)
-    const int dsid = tsid - qsid, span = dsid * K.seed_step;
-    if (span < K.seed_len) return F_UNCONNECT;
-    const int dis = sp * (tpos - qpos) - span - (sp > 0 ? qld : tld);
-    const int mat_dis = K.match_dis * (K.high_err ? dsid : 1);
-    if (dis <= mat_dis && dis >= -mat_dis) return dsid == 1 ? F_MATCH : (dsid <= K.mis3 ? F_MISMATCH : F_LONG_MISMATCH);
-    if (dis > mat_dis && dis < K.sv_len) return F_DELETE;
-    if ((dis < -mat_dis && dis >= 0 - (span - K.seed_len)) || (dis < -K.half_split && dis >= -K.sv_len)) return F_INSERT;
-    return F_UNCONNECT;
+{   // get_fseed_dis (:596-634) for two hits of the same contig and strand, the first of an earlier seed: edge_class_diag of hp_chain.h, the
+    // difference of the diagonals formed here (the callers hold relative positions)
+    const int dsid = tsid - qsid, d = tpos - qpos;
+    const int dis = (sp > 0 ? d : 0 - d) - dsid * K.seed_step - (sp > 0 ? qld : tld);
+    return edge_class_diag<false>(K, dis, dsid);
 }
 
 // do_me: frag_min_extend (:1031-1066, :1335-1343) for the cluster first -- then every hit of the cluster is kept, and for every MIN hit and
@@ -346,19 +342,144 @@ HP_INL void cluster_lane(ReadCtx &r, const EdgeK &K, const Clusters &C, HP_L int
 }
 
 // ---------------------------------------------------------------- the cluster in LDS
-// five arrays of `cap` words: W0 position relative to the cluster's first hit | W1 slot:14 j:14 dp_flag:4 |
+// five arrays of `cap` words: W0 the hit's diagonal (hit_diag of hp_chain.h: strand * (position relative to the cluster's first hit) - (seed id
+// relative to the read's first seed) * seed_step; nothing reads word 0 as a position) | W1 slot:14 j:14 dp_flag:4 |
 // W2 sid:15 len_dif:8 son_flag:5 match_flag:4 | W3 score:16 NM:16 | W4 (predecessor's index in the cluster + 1):16 node_n:16
 struct ClLds { HP_L int32_t *w0, *w1, *w2, *w3, *w4; };
 HP_INL ClLds cl_lds(HP_L int32_t *lds, int cap) { ClLds c; c.w0 = lds; c.w1 = lds + cap; c.w2 = lds + 2 * cap; c.w3 = lds + 3 * cap; c.w4 = lds + 4 * cap; return c; }
 
-HP_INL NodeS cl_unpack(int w0, int w1, int w2, int w3, int chr, int strand)
+// One block of 64 candidates (ranks i0 .. i0 + 63, their four words in q0 .. q3) against the target of seed slot x: the lane's best candidate
+// so far in bhi / blo / bi / bf and, on the '-' strand, its first match-class precursor in negp / n_i / n_f / n_hi.
+template <int SP>
+HP_INL void cl_block(const EdgeK &K, int i0, int n, int x, int t0, int tsid, int tld, int t_NM,
+                     const wv::Lane<int> &c0, const wv::Lane<int> &c1, const wv::Lane<int> &c2, const wv::Lane<int> &c3,
+                     wv::Lane<int> &bhi, wv::Lane<int> &blo, wv::Lane<int> &bi, wv::Lane<int> &bf, wv::Lane<int> &negp, wv::Lane<int> &n_i, wv::Lane<int> &n_f, wv::Lane<int> &n_hi)
 {
-    NodeS q;
-    q.pos = (int64_t)(unsigned)w0; q.chr = chr; q.slot_j = (int)((unsigned)w1 >> 4);
-    q.sid = (int16_t)((unsigned)w2 >> 17); q.strand = (int8_t)strand; q.len_dif8 = (int8_t)((w2 >> 9) & 0xff);
-    q.dp_flag = (int8_t)((int)((unsigned)w1 << 28) >> 28); q.son_flag = (uint8_t)((w2 >> 4) & 31); q.match_flag = (uint8_t)(w2 & 15); q.pad_ = 0;
-    q.score = w3 >> 16; q.NM = w3 & 0xffff;
-    return q;
+    const int dp_flag = MIN_FLAG, POSMAX = (1 << 28) - 1, NEG = -0x7fffffff;
+    WAVE_FOR(l) {
+        const int i = i0 + l;
+        const int q0 = c0[l], q1 = c1[l], q2 = c2[l], q3 = c3[l];
+        const int qslot = (int)((unsigned)q1 >> 18), qdpf = (int)((unsigned)q1 << 28) >> 28;
+        const int dsid = tsid - (int)((unsigned)q2 >> 17);
+        const int qld = (int)(int8_t)((q2 >> 9) & 0xff);
+        const int flag = edge_class_diag(K, edge_dis(q0, t0, SP > 0 ? qld : tld), dsid);     // get_fseed_dis :607-619 for a predecessor of an earlier seed
+        int ok = (i < n) & (qslot < x) & (qdpf == dp_flag) & (flag != F_UNCONNECT);
+        if (SP > 0) ok &= ((q2 >> 4) & 31) > F_MATCH_THD;                                   // '+': the candidate already has a match son, :718-720
+        const int pos = ((x - 1 - qslot) << 14) | ((q1 >> 4) & 16383);                  // scan order: seeds descending, hits ascending
+        const int cand = (q3 >> 16) + 1 + score_table(flag);
+        const int hi = ok ? (int)(((unsigned)cand << 16) | (unsigned)(65535 - ((q3 & 0xffff) + t_NM))) : NEG;   // score desc, then NM asc
+        const int lo_ = POSMAX - pos;
+        const bool better = hi > bhi[l] || (hi == bhi[l] && ok && lo_ > blo[l]);
+        bhi[l] = better ? hi : bhi[l]; blo[l] = better ? lo_ : blo[l]; bi[l] = better ? i : bi[l]; bf[l] = better ? flag : bf[l];
+        if (SP < 0) {
+            const int np = (ok & (flag <= F_MATCH_THD)) ? -pos : NEG;                    // '-': first match precursor wins, :726-733
+            const bool nb_ = np > negp[l];
+            negp[l] = nb_ ? np : negp[l]; n_i[l] = nb_ ? i : n_i[l]; n_f[l] = nb_ ? flag : n_f[l]; n_hi[l] = nb_ ? hi : n_hi[l];
+        }
+    }
+}
+
+// The target loop of dp_cluster_lds on the packed cluster, one instance per strand (a constant of the cluster):
+// the '+' body keeps no "first match precursor" state (:726-733 is '-' only), the '-' body has no son_flag test (:718-720 is '+' only).
+// lo, n, and with them the loop control and the pair count, are wave-uniform (scalar registers).  bmin: lane b = smallest seed slot of block b.
+// tests' CPU build (tests/emu/emu_edge.cpp): the pair count of a target as the sum over the blocks really scanned, beside the closed form
+#ifndef HP_PAIRS_BLOCK
+#define HP_PAIRS_BLOCK(hits) ((void)0)
+#define HP_PAIRS_TARGET(pairs, blocks_skipped) ((void)0)
+#endif
+template <int SP>
+HP_INL void cl_targets(const ClLds &L, const EdgeK &K, const HP_G int32_t *g_rnk, const HP_G int32_t *g_csrt, int lo, int n, const wv::Lane<int> &bmin, long long &pairs_)
+{
+    const int dp_flag = MIN_FLAG, NEG = -0x7fffffff;
+    const int nb = (n + 63) >> 6, last_short = 64 - (n - ((nb - 1) << 6));     // blocks of the cluster; what the last one lacks of 64 hits
+    // targets in ascending hit order (C.csrt), 64 at a time: their places in the cluster and their records.  A target's
+    // record is still what was loaded when its turn comes: only later targets (higher hit index) can choose it as their
+    // predecessor and touch its son_flag.
+    for (int o0 = 0; o0 < n; o0 += 64) {
+        wv::Lane<int> tloc, T0, T1, T2, T3;
+        WAVE_FOR(l) {
+            const int o = o0 + l; const int tl = o < n ? g_rnk[g_csrt[lo + o]] - lo : 0;
+            tloc[l] = tl; T0[l] = L.w0[tl]; T1[l] = L.w1[tl]; T2[l] = L.w2[tl]; T3[l] = L.w3[tl];
+        }
+        const int cnt = n - o0 < 64 ? n - o0 : 64;
+        for (int q = 0; q < cnt; ++q) {
+            const int t1 = wv::bcast(T1, q);
+            if ((int)((unsigned)t1 << 28) >> 28 != dp_flag) continue;
+            const int x = (int)((unsigned)t1 >> 18);
+            if (x == 0) continue;                                  // a hit of the first seed slot has no predecessor
+            // the blocks that hold a hit of an earlier seed: the others are not scanned
+            wv::Lane<int> bl;
+            WAVE_FOR(l) bl[l] = bmin[l] < x;
+            unsigned long long bm = wv::ballot(bl);
+            if (!bm) continue;
+            pairs_ += 64 * __builtin_popcountll(bm) - (((bm >> (nb - 1)) & 1) ? last_short : 0);
+            HP_PAIRS_TARGET(64 * __builtin_popcountll(bm) - (((bm >> (nb - 1)) & 1) ? last_short : 0), nb - __builtin_popcountll(bm));
+            const int ct = wv::bcast(tloc, q), t0 = wv::bcast(T0, q), t2 = wv::bcast(T2, q), t3 = wv::bcast(T3, q);
+            const int tsid = (int)((unsigned)t2 >> 17), tld = (int)(int8_t)((t2 >> 9) & 0xff), t_score = t3 >> 16, t_NM = t3 & 0xffff;
+            wv::Lane<int> bhi, blo, bi, bf, negp, n_i, n_f, n_hi;
+            WAVE_FOR(l) { bhi[l] = NEG; blo[l] = -1; bi[l] = 0; bf[l] = 0; negp[l] = NEG; n_i[l] = 0; n_f[l] = 0; n_hi[l] = 0; }
+            // a block's four words are requested together, and the next scanned block's before this one is computed: two sets of registers
+            wv::Lane<int> a0, a1, a2, a3, b0, b1, b2, b3;
+            int ia = __builtin_ctzll(bm) << 6, ib;
+            bm &= bm - 1;
+            WAVE_FOR(l) { const int i = ia + l, ii = i < n ? i : 0; a0[l] = L.w0[ii]; a1[l] = L.w1[ii]; a2[l] = L.w2[ii]; a3[l] = L.w3[ii]; }
+            for (;;) {                                             // (a last trip reads its own block again: nothing waits for that)
+                const bool more_b = bm != 0;
+                ib = more_b ? __builtin_ctzll(bm) << 6 : ia; bm &= bm - 1;
+                WAVE_FOR(l) { const int i = ib + l, ii = i < n ? i : 0; b0[l] = L.w0[ii]; b1[l] = L.w1[ii]; b2[l] = L.w2[ii]; b3[l] = L.w3[ii]; }
+                HP_PAIRS_BLOCK(n - ia < 64 ? n - ia : 64);
+                cl_block<SP>(K, ia, n, x, t0, tsid, tld, t_NM, a0, a1, a2, a3, bhi, blo, bi, bf, negp, n_i, n_f, n_hi);
+                if (!more_b) break;
+                const bool more_a = bm != 0;
+                ia = more_a ? __builtin_ctzll(bm) << 6 : ib; bm &= bm - 1;
+                WAVE_FOR(l) { const int i = ia + l, ii = i < n ? i : 0; a0[l] = L.w0[ii]; a1[l] = L.w1[ii]; a2[l] = L.w2[ii]; a3[l] = L.w3[ii]; }
+                HP_PAIRS_BLOCK(n - ib < 64 ? n - ib : 64);
+                cl_block<SP>(K, ib, n, x, t0, tsid, tld, t_NM, b0, b1, b2, b3, bhi, blo, bi, bf, negp, n_i, n_f, n_hi);
+                if (!more_a) break;
+            }
+            int max_from = -1, max_score = t_score, max_NM = t_NM, max_flag = 0;
+            bool changed = false;
+            if (SP < 0) {                                          // (the '-' strand's rule first: where it fires, and on low-error reads it mostly does, the best candidate is not looked for)
+                const int npos = wv::reduce_max(negp);
+                if (npos != NEG) {
+                    wv::Lane<int> w;
+                    WAVE_FOR(l) w[l] = negp[l] == npos;
+                    const int wl = __builtin_ctzll(wv::ballot(w));
+                    const int hi = wv::bcast(n_hi, wl);
+                    max_from = wv::bcast(n_i, wl); max_flag = wv::bcast(n_f, wl); max_score = hi >> 16; max_NM = 65535 - (hi & 0xffff);
+                    changed = true;
+                }
+            }
+            const int mh = changed ? NEG : wv::reduce_max(bhi);    // (a connectable candidate's key is above NEG: its score is within +-30 005)
+            if (!changed && mh == NEG) continue;                   // no connectable predecessor: the node keeps its state
+            if (!changed) {
+                const int cand = mh >> 16, nm = 65535 - (mh & 0xffff);
+                if (cand > max_score || (cand == max_score && nm < max_NM)) {
+                    wv::Lane<int> w;
+                    WAVE_FOR(l) w[l] = bhi[l] == mh;
+                    unsigned long long wm = wv::ballot(w);
+                    if (wm & (wm - 1)) {                           // several lanes hold the maximum: the first in scan order among them
+                        wv::Lane<int> l2;
+                        WAVE_FOR(l) l2[l] = bhi[l] == mh ? blo[l] : -1;
+                        const int ml = wv::reduce_max(l2);
+                        WAVE_FOR(l) w[l] = bhi[l] == mh && blo[l] == ml;
+                        wm = wv::ballot(w);
+                    }
+                    const int wl = __builtin_ctzll(wm);
+                    max_from = wv::bcast(bi, wl); max_flag = wv::bcast(bf, wl); max_score = cand; max_NM = nm;
+                    changed = true;
+                }
+            }
+            if (changed) {                                         // :753-761; the LDS copy is the node state until the write-back
+                const int f2 = wv::uni(L.w2[max_from]), f4 = wv::uni(L.w4[max_from]);
+                L.w2[max_from] = (f2 & ~(31 << 4)) | ((max_flag & 31) << 4);
+                L.w2[ct] = (t2 & ~15) | (max_flag & 15);
+                L.w3[ct] = (int)(((unsigned)max_score << 16) | ((unsigned)max_NM & 0xffffu));
+                L.w4[ct] = ((max_from + 1) << 16) | (((f4 & 0xffff) + 1) & 0xffff);
+                wv::sync();
+            }
+        }
+    }
 }
 
 // One cluster [lo, lo + n) (ranks), n <= lds_words / 5: frag_dp_update (:701-764) for its MIN hits, out of LDS.
@@ -366,17 +487,27 @@ HP_INL NodeS cl_unpack(int w0, int w1, int w2, int w3, int chr, int strand)
 // do_me: frag_min_extend (:1031-1066, :1335-1343) for the cluster first, on the packed records: the cluster's repetitive (MULTI) hits are
 // listed in ascending hit order -- a few dozen at a read's true locus, where most hits are the only ones of their seeds -- and every MIN
 // hit is compared with that list only; "first hit of its seed" is a segmented ballot over the list, carried across its 64-hit chunks.
-HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool do_me)
+HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo_, int n_, bool do_me_)
 {
+    const int lo = wv::uni(lo_), n = wv::uni(n_); const bool do_me = wv::uni(do_me_) != 0;      // the arguments arrive in vector registers
     const HP_G NodeS *ns = (const HP_G NodeS *)r.nd;
     HP_G NodeS *gd = (HP_G NodeS *)r.nd;
     const HP_G int32_t *g_srt = (const HP_G int32_t *)r.srt, *g_rnk = (const HP_G int32_t *)r.rnk, *g_csrt = (const HP_G int32_t *)C.csrt;
     const HP_G int16_t *g_hnm = (const HP_G int16_t *)r.h_nm;
     HP_G int32_t *g_from = (HP_G int32_t *)r.n_from, *g_node_n = (HP_G int32_t *)r.n_node_n;
     const ClLds L = cl_lds(r.cx.lds, r.cx.lds_words / 5);
-    const EdgeK K = edge_consts(r.cx.P);
-    const int dp_flag = MIN_FLAG;
-    if ((long long)(r.seed_id[r.seed_out - 1] - r.seed_id[0] + 1) * K.seed_step > 0x3fffffffll) return false;     // 32-bit geometry below
+    const EdgeK K = edge_uni(edge_consts(r.cx.P));
+#ifdef HP_PROF_EDGE
+    long long te_ = wv::clock();
+#define HP_ESTAMP(k) do { const long long now_ = wv::clock(); if (r.prof) r.prof[(k)] += now_ - te_; te_ = now_; } while (0)
+#else
+#define HP_ESTAMP(k) do { } while (0)
+#endif
+    if ((long long)(r.seed_id[r.seed_out - 1] - r.seed_id[0] + 1) * K.seed_step > 0x3fffffffll || !edge_k24(K)) return false;     // 32-bit geometry below
+    // The diagonals stay inside int32: a packed hit has 0 <= rel <= 0x3fffff00 and 0 <= (sid - sid0) * seed_step <= 0x3fffffff (the line above), so
+    // D = +-rel - (sid - sid0) * seed_step lies in [-0x7ffffeff, 0x3fffff00]; D_t - D_q = +-(rel_t - rel_q) - dsid * seed_step is at most
+    // 0x3fffff00 + 0x3fffffff = 0x7ffffeff in magnitude, and |len_dif| <= 128 keeps D_t - D_q - ld above -2^31 and below 2^31.
+    const int sid0 = r.seed_id[0];
     // ---- load + pack; lane b of `bmin` keeps the smallest seed slot of block b (64 consecutive ranks)
     const NodeS first = node_load(ns + g_srt[lo]);
     const int64_t pos0 = first.pos; const int strand = first.strand;
@@ -393,9 +524,9 @@ HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool 
                 const int id = g_srt[lo + i];
                 const NodeS q = node_load(ns + id);
                 const int64_t rel = q.pos - pos0;
-                bv = rel < 0 || rel > 0x7ffffff0ll || q.score < -30000 || q.score > 30000 || q.NM < 0 || q.NM > 65535 || q.sid < 0;
+                bv = rel < 0 || rel > 0x3fffff00ll || q.score < -30000 || q.score > 30000 || q.NM < 0 || q.NM > 65535 || q.sid < 0;
                 nmv = g_hnm[id]; sv = 0 - (q.slot_j >> 14);
-                L.w0[i] = (int)(unsigned)rel;
+                L.w0[i] = hit_diag(K, strand, (int)rel, q.sid - sid0);
                 L.w1[i] = (int)(((unsigned)q.slot_j << 4) | ((unsigned)q.dp_flag & 15u));
                 L.w2[i] = (int)(((unsigned)(unsigned short)q.sid << 17) | (((unsigned)q.len_dif8 & 255u) << 9) | (((unsigned)q.son_flag & 31u) << 4) | ((unsigned)q.match_flag & 15u));
                 L.w3[i] = (int)(((unsigned)q.score << 16) | ((unsigned)q.NM & 0xffffu));
@@ -410,8 +541,9 @@ HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool 
     }
     if (bad || nm_sum > 65535 || n > 64 * 64) return false;       // a chain's NM is at most the sum over the cluster: 16 bits suffice
     wv::sync();
-    const int sp = strand, POSMAX = (1 << 28) - 1, NEG = -0x7fffffff;
+    const int sp = strand;
     long long pairs_ = 0;                                      // accounting, flushed once (a counter in r is a memory round trip per use)
+    HP_ESTAMP(16);
     if (do_me) {
         const size_t mark = arena_mark(r.cx.tmp);
         int32_t *ml = (int32_t *)arena_alloc(r.cx, sizeof(int32_t) * 2 * (size_t)(n + 64));      // places of the MULTI hits, then one mark each
@@ -469,10 +601,9 @@ HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool 
                             int v = 0;
                             if (sd[l] >= 0 && sd[l] != xm) {
                                 const bool q_first = sd[l] < xm;                       // the hit of the earlier seed is `pre` (get_fseed_dis :607-619)
-                                const int dsid = q_first ? msid - qsid[l] : qsid[l] - msid, span = dsid * K.seed_step;
-                                const int dis = (q_first ? sp * (m0 - q0[l]) : sp * (q0[l] - m0)) - span - (sp > 0 ? (q_first ? qld[l] : mld) : (q_first ? mld : qld[l]));
-                                const int mat_dis = K.match_dis * (K.high_err ? dsid : 1);
-                                v = span >= K.seed_len && dis <= mat_dis && dis >= -mat_dis;
+                                const int dsid = q_first ? msid - qsid[l] : qsid[l] - msid;
+                                const int ld = sp > 0 ? (q_first ? qld[l] : mld) : (q_first ? mld : qld[l]);
+                                v = edge_match_diag(K, q_first ? edge_dis(q0[l], m0, ld) : edge_dis(m0, q0[l], ld), dsid);
                             }
                             q[l] = v;
                         }
@@ -499,94 +630,11 @@ HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool 
         }
         arena_release(r.cx.tmp, mark);
     }
-    // ---- targets in ascending hit order (C.csrt), 64 at a time: their places in the cluster and their records.  A target's
-    // record is still what was loaded when its turn comes: only later targets (higher hit index) can choose it as their
-    // predecessor and touch its son_flag.
-    for (int o0 = 0; o0 < n; o0 += 64) {
-        wv::Lane<int> tloc, T0, T1, T2, T3;
-        WAVE_FOR(l) {
-            const int o = o0 + l; const int tl = o < n ? g_rnk[g_csrt[lo + o]] - lo : 0;
-            tloc[l] = tl; T0[l] = L.w0[tl]; T1[l] = L.w1[tl]; T2[l] = L.w2[tl]; T3[l] = L.w3[tl];
-        }
-        const int cnt = n - o0 < 64 ? n - o0 : 64;
-        for (int q = 0; q < cnt; ++q) {
-            const int t1 = wv::bcast(T1, q);
-            if ((int)((unsigned)t1 << 28) >> 28 != dp_flag) continue;
-            const int x = (int)((unsigned)t1 >> 18);
-            if (x == 0) continue;                                  // a hit of the first seed slot has no predecessor
-            const int ct = wv::bcast(tloc, q), t0 = wv::bcast(T0, q), t2 = wv::bcast(T2, q), t3 = wv::bcast(T3, q);
-            const int tsid = (int)((unsigned)t2 >> 17), tld = (int)(int8_t)((t2 >> 9) & 0xff), t_score = t3 >> 16, t_NM = t3 & 0xffff;
-            wv::Lane<int> bhi, blo, bi, bf, negp, n_i, n_f, n_hi, okl;
-            WAVE_FOR(l) { bhi[l] = NEG; blo[l] = -1; bi[l] = 0; bf[l] = 0; negp[l] = NEG; n_i[l] = 0; n_f[l] = 0; n_hi[l] = 0; okl[l] = 0; }
-            for (int i0 = 0; i0 < n; i0 += 64) {
-                if (wv::bcast(bmin, i0 >> 6) >= x) continue;       // no hit of an earlier seed in this block
-                pairs_ += n - i0 < 64 ? n - i0 : 64;
-                WAVE_FOR(l) {
-                    const int i = i0 + l, ii = i < n ? i : 0;
-                    const int q0 = L.w0[ii], q1 = L.w1[ii], q2 = L.w2[ii], q3 = L.w3[ii];
-                    const int qslot = (int)((unsigned)q1 >> 18), qdpf = (int)((unsigned)q1 << 28) >> 28;
-                    const int dsid = tsid - (int)((unsigned)q2 >> 17);
-                    const int span = dsid * K.seed_step;
-                    const int qld = (int)(int8_t)((q2 >> 9) & 0xff);
-                    const int dis = sp * (t0 - q0) - span - (sp > 0 ? qld : tld);               // get_fseed_dis :607-619 for a predecessor of an earlier seed
-                    const int mat_dis = K.match_dis * (K.high_err ? dsid : 1);
-                    int flag = F_UNCONNECT;
-                    if (span >= K.seed_len) {
-                        if (dis <= mat_dis && dis >= -mat_dis) flag = dsid == 1 ? F_MATCH : (dsid <= K.mis3 ? F_MISMATCH : F_LONG_MISMATCH);
-                        else if (dis > mat_dis && dis < K.sv_len) flag = F_DELETE;
-                        else if ((dis < -mat_dis && dis >= 0 - (span - K.seed_len)) || (dis < -K.half_split && dis >= -K.sv_len)) flag = F_INSERT;
-                    }
-                    const int ok = (i < n) & (qslot < x) & (qdpf == dp_flag) & !((sp == 1) & (((q2 >> 4) & 31) <= F_MATCH_THD)) & (flag != F_UNCONNECT);
-                    const int pos = ((x - 1 - qslot) << 14) | ((q1 >> 4) & 16383);                  // scan order: seeds descending, hits ascending
-                    const int cand = (q3 >> 16) + 1 + score_table(flag);
-                    const int hi = ok ? (int)(((unsigned)cand << 16) | (unsigned)(65535 - ((q3 & 0xffff) + t_NM))) : NEG;   // score desc, then NM asc
-                    const int lo_ = POSMAX - pos;
-                    const bool better = hi > bhi[l] || (hi == bhi[l] && ok && lo_ > blo[l]);
-                    bhi[l] = better ? hi : bhi[l]; blo[l] = better ? lo_ : blo[l]; bi[l] = better ? i : bi[l]; bf[l] = better ? flag : bf[l];
-                    const int np = (ok & (sp == -1) & (flag <= F_MATCH_THD)) ? -pos : NEG;          // '-': first match precursor wins, :726-733
-                    const bool nb = np > negp[l];
-                    negp[l] = nb ? np : negp[l]; n_i[l] = nb ? i : n_i[l]; n_f[l] = nb ? flag : n_f[l]; n_hi[l] = nb ? hi : n_hi[l];
-                    okl[l] |= ok;
-                }
-            }
-            if (wv::ballot(okl) == 0) continue;                    // no connectable predecessor: the node keeps its state
-            int max_from = -1, max_score = t_score, max_NM = t_NM, max_flag = 0;
-            bool changed = false;
-            const int npos = wv::reduce_max(negp);
-            if (npos != NEG) {
-                wv::Lane<int> w;
-                WAVE_FOR(l) w[l] = negp[l] == npos;
-                const int wl = __builtin_ctzll(wv::ballot(w));
-                const int hi = wv::bcast(n_hi, wl);
-                max_from = wv::bcast(n_i, wl); max_flag = wv::bcast(n_f, wl); max_score = hi >> 16; max_NM = 65535 - (hi & 0xffff);
-                changed = true;
-            } else {
-                const int mh = wv::reduce_max(bhi);
-                if (mh != NEG) {
-                    const int cand = mh >> 16, nm = 65535 - (mh & 0xffff);
-                    if (cand > max_score || (cand == max_score && nm < max_NM)) {
-                        wv::Lane<int> l2;
-                        WAVE_FOR(l) l2[l] = bhi[l] == mh ? blo[l] : -1;
-                        const int ml = wv::reduce_max(l2);
-                        wv::Lane<int> w;
-                        WAVE_FOR(l) w[l] = bhi[l] == mh && blo[l] == ml;
-                        const int wl = __builtin_ctzll(wv::ballot(w));
-                        max_from = wv::bcast(bi, wl); max_flag = wv::bcast(bf, wl); max_score = cand; max_NM = nm;
-                        changed = true;
-                    }
-                }
-            }
-            if (changed) {                                         // :753-761; the LDS copy is the node state until the write-back
-                const int f2 = wv::uni(L.w2[max_from]), f4 = wv::uni(L.w4[max_from]);
-                L.w2[max_from] = (f2 & ~(31 << 4)) | ((max_flag & 31) << 4);
-                L.w2[ct] = (t2 & ~15) | (max_flag & 15);
-                L.w3[ct] = (int)(((unsigned)max_score << 16) | ((unsigned)max_NM & 0xffffu));
-                L.w4[ct] = ((max_from + 1) << 16) | (((f4 & 0xffff) + 1) & 0xffff);
-                wv::sync();
-            }
-        }
-    }
+    HP_ESTAMP(17);
+    // ---- the targets, by the loop body of the cluster's strand
+    if (sp > 0) cl_targets<1>(L, K, g_rnk, g_csrt, lo, n, bmin, pairs_); else cl_targets<-1>(L, K, g_rnk, g_csrt, lo, n, bmin, pairs_);
     r.n_pairs += pairs_;
+    HP_ESTAMP(18);
     // ---- write back: the dynamic half of the record, predecessor and node count
     wv::sync();
     for (int i0 = 0; i0 < n; i0 += 64) {
@@ -605,6 +653,8 @@ HP_NOINL bool dp_cluster_lds(ReadCtx &r, const Clusters &C, int lo, int n, bool 
         }
     }
     wv::sync();
+    HP_ESTAMP(19);
+#undef HP_ESTAMP
     return true;
 }
 

@@ -55,6 +55,9 @@ struct Ctx {
     int lds_epoch;            // bumped by every DP routine that writes the rows' part of the LDS (hp_ksw.h): what a caller parked there (frags_merge's staged CIGARs) is gone
 };
 // -DHP_PROF_FILL: slots 16 .. 23 time parts of frags_merge (hp_fill.h) instead of parts of the chaining (hp_chain.h, hp_gaps.h)
+#if defined(HP_PROF_EDGE) && (defined(HP_PROF_TRACK) || defined(HP_PROF_FILL))
+#error "-DHP_PROF_EDGE, -DHP_PROF_TRACK and -DHP_PROF_FILL all use prof slots 16 .. 23: one of them per build"
+#endif
 #ifdef HP_PROF_FILL
 #define HP_PROF_CHAIN_ON 0
 #define HP_TADD_FILL(cx, slot, v) HP_TADD(cx, slot, v)

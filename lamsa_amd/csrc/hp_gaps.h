@@ -529,7 +529,7 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
     if (!anc) { arena_release(cx.tmp, mark); return -1; }
     int32_t *anc_x = anc + (H + 2);
     int A = 0;
-#if defined(HP_PROF) && !defined(HP_PROF_TRACK)
+#if defined(HP_PROF) && !defined(HP_PROF_TRACK) && !defined(HP_PROF_EDGE)
     long long tl_ = wv::clock();
 #define HP_LSTAMP(k) do { const long long now_ = wv::clock(); if (r.prof) r.prof[(k)] += now_ - tl_; tl_ = now_; } while (0)
 #else
@@ -572,7 +572,7 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
     for (int i0 = 0; i0 < A; i0 += 64) { WAVE_FOR(l) { if (i0 + l < A) g_ancx[i0 + l] = g_seed[g_anc[i0 + l]]; } }
     wv::sync();
     HP_LSTAMP(16);
-#if defined(HP_PROF) && !defined(HP_PROF_TRACK)
+#if defined(HP_PROF) && !defined(HP_PROF_TRACK) && !defined(HP_PROF_EDGE)
     if (HP_PROF_CHAIN_ON && r.prof) { r.prof[21] += 1; r.prof[12] += A; }
 #endif
     // Most lines of a read against a repeat-rich genome are a few hits of neighbouring seed slots at some repeat copy: no gap at all.
@@ -589,7 +589,7 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
             wv::sync();
             arena_release(cx.tmp, mark);
             HP_LSTAMP(17);
-#if defined(HP_PROF) && !defined(HP_PROF_TRACK)
+#if defined(HP_PROF) && !defined(HP_PROF_TRACK) && !defined(HP_PROF_EDGE)
             if (HP_PROF_CHAIN_ON && r.prof) r.prof[22] += 1;
 #endif
             return A;
@@ -627,7 +627,7 @@ HP_HOT int line_build(ReadCtx &r, int max_node, int32_t *ln, int32_t *_line, int
     }
     wv::sync();
     HP_LSTAMP(17);
-#if defined(HP_PROF) && !defined(HP_PROF_TRACK)
+#if defined(HP_PROF) && !defined(HP_PROF_TRACK) && !defined(HP_PROF_EDGE)
     if (HP_PROF_CHAIN_ON && r.prof) { r.prof[23] += G; if (G < HP_GAP_MIN) r.prof[54] += G; r.prof[55] += 1; }
 #endif
     // ---- the mini DPs.  By cluster when the read's hits have been clustered (gaps_by_cluster above); else every gap scans its own seed range:
