@@ -177,7 +177,20 @@ typedef struct lamsa_hp_batch {
  * A gap never consumes the M before it, so it never merges with or crosses another gap or a clip and never reaches the
  * record's start; a gap that touches another gap or a clip stays and stops its neighbours.  A mismatch inside a stretch
  * that a deletion of k bases moved across keeps its base and gets ref_off + k.  Gaps are not right-aligned or merged, and
- * where the records of a line meet is not touched.  The mismatch lists and the =/X form describe the shifted alignment. */
+ * where the records of a line meet is not touched.  The mismatch lists and the =/X form describe the shifted alignment.
+ * With LAMSA_HP_TAG_SUMMARY set, a record is exactly 15 words and no CIGAR word follows cigar_n:
+ *     offset_lo, offset_hi, chr, nstrand, score, NM, cigar_n,
+ *     q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs
+ * cigar_n is the element count of the record's M-form CIGAR, the one the stream ships without the item, and the eight
+ * words behind it are defined on that CIGAR: q_beg .. q_end the covered read interval, 1-based and inclusive, on the
+ * read as given (a '+' record: leading S + 1 .. read length - trailing S; a '-' record: the two clips swapped; an
+ * empty CIGAR: 1 .. read length); ref_span the sum of the M and D lengths; m_bases, ins_bases, del_bases the sums of
+ * the M / I / D lengths; ins_runs, del_runs the numbers of I / D elements (an I next to a D is two runs).  For every
+ * record the device makes, n_mm = NM - ins_bases - del_bases >= 0 is its number of mismatches and
+ *     score = (m_bases - n_mm) * match - n_mm * mis - ins_runs * ins_gapo - ins_bases * ins_gape
+ *             - del_runs * del_gapo - del_bases * del_gape.
+ * Line headers, the per-read header and the status are what they are without the item.  It is what a PAF
+ * line needs, without the CIGAR words. */
 typedef struct lamsa_hp_result {
     const int32_t *stream; int64_t stream_words;
     const int64_t *read_off;      /* [n_reads] start of read r's stream */
@@ -195,11 +208,15 @@ int lamsa_hp_align_batch(lamsa_hp_handle *h, const lamsa_hp_batch *batch, lamsa_
  * writer needs for MD:Z without reading the reference again).  LAMSA_HP_TAG_EQX: the CIGARs are in =/X form (the
  * device splits the M elements by the same lists, which are in the stream only if LAMSA_HP_TAG_MISMATCHES is set too).
  * LAMSA_HP_TAG_LEFT_ALIGN: the gaps of every CIGAR are left-aligned (the device shifts them before it counts; no word
- * is added).  The items combine freely.  Flags outside the three (4 among them): LAMSA_HP_EINVAL; so while a batch or
- * run is in flight. */
+ * is added).  These three combine freely.  LAMSA_HP_TAG_SUMMARY: every record is its fixed 15-word summary in place
+ * of its CIGAR (above).  With LAMSA_HP_TAG_MISMATCHES or LAMSA_HP_TAG_EQX it is LAMSA_HP_EINVAL (there is nothing to
+ * list or split); with LAMSA_HP_TAG_LEFT_ALIGN it is accepted and the stream is word for word that of
+ * LAMSA_HP_TAG_SUMMARY alone, since left alignment changes M lengths only (the device skips the shift).  Flags outside
+ * the four (4, 16 and 64 among them): LAMSA_HP_EINVAL; so while a batch or run is in flight. */
 #define LAMSA_HP_TAG_MISMATCHES 1
 #define LAMSA_HP_TAG_EQX 2
 #define LAMSA_HP_TAG_LEFT_ALIGN 8
+#define LAMSA_HP_TAG_SUMMARY 32
 int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags);
 
 /* The same in two steps, so that a caller can keep a batch resident in HBM and overlap or

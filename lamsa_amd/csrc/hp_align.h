@@ -68,11 +68,28 @@ HP_NOINL void regs_remain(ReadCtx &r, Regs &G, int min_thd, int max_thd)
 struct OutBuf { int32_t *w; int n, cap; };
 HP_INL void out_put(Ctx &cx, OutBuf &o, int32_t v) { if (o.n < o.cap) o.w[o.n++] = v; else cx.status |= ST_OVERFLOW; }
 
+enum { HP_SUMREC_WORDS = 15 };   // a record under LAMSA_HP_TAG_SUMMARY: the 7 header words and the 8 of Rec::sum (include/lamsa_hp.h)
 HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
 {
     out_put(cx, o, la.line_score); out_put(cx, o, la.tol_score); out_put(cx, o, la.tol_NM); out_put(cx, o, la.cur_res_n + 1);
     for (int j = 0; j <= la.cur_res_n; ++j) {
         const Rec &rec = la.rec[j];
+        if (la.tags & LAMSA_HP_TAG_SUMMARY) {                         // the record's 15 words, one per lane, in one store; its CIGAR stays where it is
+            if (o.n + HP_SUMREC_WORDS <= o.cap) {
+                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
+                const HP_G int32_t *sum = (const HP_G int32_t *)rec.sum;      // (written by every lane in res_aux: a lane reads its own store)
+                const int32_t lo = (int32_t)(rec.offset & 0xffffffffll), hi = (int32_t)(rec.offset >> 32);
+                WAVE_FOR(l) {
+                    int32_t v = l >= 7 && l < HP_SUMREC_WORDS ? sum[l - 7] : 0;
+                    v = l == 0 ? lo : l == 1 ? hi : l == 2 ? rec.chr : l == 3 ? rec.nstrand : l == 4 ? rec.score : l == 5 ? rec.NM : l == 6 ? rec.cig.n : v;
+                    if (l < HP_SUMREC_WORDS) dst[l] = v;
+                }
+                o.n += HP_SUMREC_WORDS;
+                wv::sync();
+            }
+            else cx.status |= ST_OVERFLOW;
+            continue;
+        }
         out_put(cx, o, (int32_t)(rec.offset & 0xffffffffll)); out_put(cx, o, (int32_t)(rec.offset >> 32));
         out_put(cx, o, rec.chr); out_put(cx, o, rec.nstrand); out_put(cx, o, rec.score); out_put(cx, o, rec.NM);
         if (la.tags & LAMSA_HP_TAG_EQX) {                             // the CIGAR in =/X form (hp_eqx.h): cigar_n is known once the words are written
@@ -113,13 +130,26 @@ HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
 // line cover disjoint parts of the read -- and what the items add to the line's result words: LAMSA_HP_TAG_MISMATCHES the lists and a
 // count per record, LAMSA_HP_TAG_EQX at most two words per mismatch (a record has at most cigar_n + 2 n_mm words, hp_eqx.h)
 // LAMSA_HP_TAG_LEFT_ALIGN adds no word and needs no list.
+// LAMSA_HP_TAG_SUMMARY: a record is HP_SUMREC_WORDS words whatever its CIGAR holds, so a line of the phased fill is at most
+// 4 + 15 * HP_REC_MAX words and the PH_REG_WORDS * HP_REC_MAX of its covered intervals: line_sum_words on top of the flag-off capacity holds
+// that for every read length, a read of a few bases included (12 L alone does not).  On the one-kernel path and in the batch's stream the term
+// in L stays as it is (the buffers do not shrink under the item): it pays the 8 words that stand for a CIGAR wherever the CIGARs of the read's
+// records have 8 elements on average, and read_sum_words per read (times the scale) pays them for a full line of HP_REC_MAX records of
+// fewer elements.  A read with more such records than that is short of words as any other: ST_OVERFLOW, the second pass.
 enum { HP_TAGS_LISTS = LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX };
+// the items as the fill applies them: under LAMSA_HP_TAG_SUMMARY no CIGAR is shipped and left alignment changes M lengths only -- not a word
+// of a summary (include/lamsa_hp.h) -- so the shift is skipped; the item never comes with a list item (lamsa_hp_set_result_tags)
+HP_HD int fill_tags(int t) { return (t & LAMSA_HP_TAG_SUMMARY) ? LAMSA_HP_TAG_SUMMARY : t & (HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN); }
+// what lamsa_hp_set_result_tags accepts: the four items, LAMSA_HP_TAG_SUMMARY with neither item of HP_TAGS_LISTS (nothing to list or split)
+HP_HD bool result_tags_valid(int t) { return !(t & ~(HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN | LAMSA_HP_TAG_SUMMARY)) && !((t & LAMSA_HP_TAG_SUMMARY) && (t & HP_TAGS_LISTS)); }
 HP_INL int line_ev_cap(int L) { return L + 64; }
 HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
 HP_INL int line_eqx_words(int L) { return 2 * (L + 64); }
-HP_INL int line_tag_words(int L, int tags) { return ((tags & LAMSA_HP_TAG_MISMATCHES) ? line_ev_words(L) : 0) + ((tags & LAMSA_HP_TAG_EQX) ? line_eqx_words(L) : 0); }
+HP_HD int line_sum_words() { return HP_SUMREC_WORDS * HP_REC_MAX; }
+HP_HD int read_sum_words() { return 8 * HP_REC_MAX; }
+HP_INL int line_tag_words(int L, int tags) { return ((tags & LAMSA_HP_TAG_MISMATCHES) ? line_ev_words(L) : 0) + ((tags & LAMSA_HP_TAG_EQX) ? line_eqx_words(L) : 0) + ((tags & LAMSA_HP_TAG_SUMMARY) ? line_sum_words() : 0); }
 // words of a read's result stream on the one-kernel path (align_read); the second pass sizes its arena by it
-HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + ((tags & LAMSA_HP_TAG_MISMATCHES) ? 4LL * L + 4 * HP_REC_MAX : 0) + ((tags & LAMSA_HP_TAG_EQX) ? 8LL * L + 512 : 0)) * scale; }
+HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + ((tags & LAMSA_HP_TAG_MISMATCHES) ? 4LL * L + 4 * HP_REC_MAX : 0) + ((tags & LAMSA_HP_TAG_EQX) ? 8LL * L + 512 : 0) + ((tags & LAMSA_HP_TAG_SUMMARY) ? read_sum_words() : 0)) * scale; }
 
 // frag_check over all lines of one round (frag_check.c:886-955) + get_reg (lamsa_aln.c:597) for round 1
 HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
@@ -245,7 +275,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
     if (skip) { cx.status |= ST_UNSUPPORTED; r.H = 0; r.seed_out = 0; }
     const int H = r.H;
     // read-lifetime allocations
-    const int tags = a.in.tags & (HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN);
+    const int tags = fill_tags(a.in.tags);
     const int out_cap = (int)read_out_cap(r.L, a.scale, tags);
     OutBuf o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);

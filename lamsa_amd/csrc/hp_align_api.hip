@@ -343,13 +343,17 @@ static int grow(lamsa_hp_handle *h, DevBuf &b, size_t bytes)
 // result + CIGAR bytes per read base of a wave's scratch; `eqx`: what the =/X words of LAMSA_HP_TAG_EQX add (a line's: 2 words per base,
 // line_eqx_words; a read's on the one-kernel path: 8, read_out_cap)
 static size_t tag_slab_per_base(int tags, int eqx) { return (size_t)((tags & HP_TAGS_LISTS) ? 152 : 128) + ((tags & LAMSA_HP_TAG_EQX) ? (size_t)eqx : 0); }
+// LAMSA_HP_TAG_SUMMARY costs nothing per base.  Per wave it adds the words its capacities add to the result buffers (hp_align.h): a line's
+// line_sum_words on the phased fill, read_sum_words times the scale on the one-kernel path.  (Rec::sum, 8 words in each of a LineRes's
+// HP_REC_MAX records with or without the item, is 2 KiB of the slabs' constant 256 KiB, of which the fixed-size records took under 16.)
+static size_t tag_slab_fixed(int tags, int scale, bool phased) { return (tags & LAMSA_HP_TAG_SUMMARY) ? sizeof(int32_t) * (size_t)(phased ? line_sum_words() : read_sum_words() * scale) : 0; }
 static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale, int tags)
 {   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base; 24 more with the
     // mismatch lists of LAMSA_HP_TAG_MISMATCHES or LAMSA_HP_TAG_EQX, 40 more for the =/X words of LAMSA_HP_TAG_EQX: read_out_cap), and the direction matrix
     // of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
     // Reads that need more flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
     const size_t z = (2 * (size_t)P.band_w + 128) * ((size_t)L + 256);
-    return al256(((size_t)256 << 10) + (size_t)scale * tag_slab_per_base(tags, 40) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
+    return al256(((size_t)256 << 10) + tag_slab_fixed(tags, scale, false) + (size_t)scale * tag_slab_per_base(tags, 40) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
 }
 
 // validate `B`, build its processing order and sort index, copy it into slot `T` on the copy stream
@@ -570,10 +574,12 @@ static PhasedLayout phased_layout(int n, int64_t n_hits, int64_t n_bases, int64_
     return Y;
 }
 // words of a batch's result stream; the mismatch lists (LAMSA_HP_TAG_MISMATCHES) are at most one word per aligned base and a count per record,
-// the =/X pieces (LAMSA_HP_TAG_EQX) at most two words per aligned base
+// the =/X pieces (LAMSA_HP_TAG_EQX) at most two words per aligned base.  LAMSA_HP_TAG_SUMMARY: 8 words per record stand for its CIGAR; the 4
+// words per base stay and pay them as they paid the CIGARs, and read_sum_words per read pays them for a full line of short records (hp_align.h)
 static int64_t main_stream_cap(int n, int64_t n_bases, int tags)
 {
-    return 1024 + (int64_t)n * 256 + 4 * n_bases + ((tags & LAMSA_HP_TAG_MISMATCHES) ? (int64_t)n * 128 + 2 * n_bases : 0) + ((tags & LAMSA_HP_TAG_EQX) ? (int64_t)n * 128 + 4 * n_bases : 0);
+    return 1024 + (int64_t)n * 256 + 4 * n_bases + ((tags & LAMSA_HP_TAG_MISMATCHES) ? (int64_t)n * 128 + 2 * n_bases : 0) + ((tags & LAMSA_HP_TAG_EQX) ? (int64_t)n * 128 + 4 * n_bases : 0) +
+           ((tags & LAMSA_HP_TAG_SUMMARY) ? (int64_t)n * read_sum_words() : 0);
 }
 
 // The main pass of the batch in slot `T` as the five launches of hp_phase.h, with the launch resources of slot `Ln`.
@@ -606,7 +612,7 @@ static SlabPlan slab_plan(lamsa_hp_handle *h, int max_L, int max_H, bool shared 
     // itself, a lane-DP group's buffers.  Wave jobs: an ordinary slab takes the junctions and the end extensions of a few thousand rows; the
     // direction matrix of the longest end extension (the whole read long) lives in one of the big slabs that only the first waves own.
     Q.chain = al256(((size_t)256 << 10) + 128 * (size_t)max_L + 424 * (size_t)max_H);
-    Q.fill = al256(((size_t)256 << 10) + tag_slab_per_base(h->result_tags, 16) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
+    Q.fill = al256(((size_t)256 << 10) + tag_slab_fixed(h->result_tags, 1, true) + tag_slab_per_base(h->result_tags, 16) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
     { static const int kb = getenv("LAMSA_HP_WJ_SLAB_KB") ? atoi(getenv("LAMSA_HP_WJ_SLAB_KB")) : 0;    // diagnostic
       Q.wj = ((size_t)(kb > 0 ? kb : 1024) << 10) + 33 * 256; }
     Q.wjb = al256((size_t)wj_need(&P, WJ_HEAD, max_L, max_L + 2 * P.hash_step + 64) + ((size_t)64 << 10)) + 33 * 256;
@@ -982,7 +988,8 @@ extern "C" int lamsa_hp_set_scratch_limit(lamsa_hp_handle *h, size_t bytes)
 
 extern "C" int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags)
 {
-    if (!h || (flags & ~(LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX | LAMSA_HP_TAG_LEFT_ALIGN))) return LAMSA_HP_EINVAL;
+    if (!h) return LAMSA_HP_EINVAL;
+    if (!result_tags_valid(flags)) { h->err = "result tags: an unknown item, or LAMSA_HP_TAG_SUMMARY (no CIGAR is shipped) with an item that lists or splits"; return LAMSA_HP_EINVAL; }
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight: collect them first"; return LAMSA_HP_EINVAL; }
     h->result_tags = flags;

@@ -27,11 +27,13 @@ namespace hp {
 struct Rec {                     // res_t, frag_check.h:46-59
     int64_t offset, refend; int32_t chr, nstrand, readend, score, NM; CigV cig;
     int32_t *mm; int32_t n_mm;   // with LineRes::ev: the record's mismatches (ref_off << 2 | base), a view into ev like the CIGARs
+    int32_t sum[8];              // set by res_aux from what it counts anyway: q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs
+                                 // (the last eight words of a record under LAMSA_HP_TAG_SUMMARY, include/lamsa_hp.h; out_line, hp_align.h)
 };
 struct LineRes {                 // line_aln_res, frag_check.h:61-73
     int line_score, tol_score, tol_NM, cur_res_n;
     int32_t *ev; int ev_cap;     // set by the caller: buffer for the mismatch lists of the line's records (LAMSA_HP_TAG_MISMATCHES and LAMSA_HP_TAG_EQX need them), or nullptr
-    int tags;                    // set by the caller: the LAMSA_HP_TAG_* items out_line writes (lists shipped / CIGARs in =/X form) and res_aux applies (gaps left-aligned)
+    int tags;                    // set by the caller: the LAMSA_HP_TAG_* items out_line writes (lists shipped / CIGARs in =/X form / summaries in place of CIGARs) and res_aux applies (gaps left-aligned)
     Rec rec[HP_REC_MAX];
 };
 
@@ -1137,6 +1139,12 @@ HP_NOINL bool res_aux(ReadCtx &r, LineRes &la)
         if (bad || read_i != r.L || ref_i != ref_len) { cx.status |= ST_REFEXIT; return false; }
         rec.NM = n_mm + n_ie + n_de;
         rec.score = n_m * P->match - n_mm * P->mis - n_io * P->ins_gapo - n_ie * P->ins_gape - n_do * P->del_gapo - n_de * P->del_gape;
+        {   // the record's summary: the covered read interval on the read as given (push_reg_res, lamsa_aln.c:571: the clips swap on '-') and the counts
+            const int w0 = cn > 0 ? (int)gc[0] : 0, w1 = cn > 0 ? (int)gc[cn - 1] : 0;       // (an empty CIGAR: 1 .. L)
+            const int s0 = (w0 & 0xf) == C_S ? w0 >> 4 : 0, s1 = (w1 & 0xf) == C_S ? w1 >> 4 : 0;
+            rec.sum[0] = (rec.nstrand == 1 ? s0 : s1) + 1; rec.sum[1] = r.L - (rec.nstrand == 1 ? s1 : s0);
+            rec.sum[2] = ref_len; rec.sum[3] = n_m + n_mm; rec.sum[4] = n_ie; rec.sum[5] = n_de; rec.sum[6] = n_io; rec.sum[7] = n_do;
+        }
         if (ev) {
             if (ev_n > la.ev_cap) { cx.status |= ST_OVERFLOW; return false; }
             rec.mm = la.ev + ev0; rec.n_mm = ev_n - ev0;

@@ -257,8 +257,8 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
     flines_bind(F, a.fl_base + M.fl_off[round], F.n, M.fl_tot[round]);
     F.jarena = a.job_base;
     const int cur_cap = 2 * r.L + 512;
-    const int tags = a.in.tags & HP_TAGS_LISTS;                                          // either item needs the line's mismatch lists
-    const int out_cap = 64 + 12 * r.L + PH_REG_WORDS * HP_REC_MAX + line_tag_words(r.L, tags);
+    const int all_tags = fill_tags(a.in.tags), tags = all_tags & HP_TAGS_LISTS;          // either item of HP_TAGS_LISTS needs the line's mismatch lists
+    const int out_cap = 64 + 12 * r.L + PH_REG_WORDS * HP_REC_MAX + line_tag_words(r.L, all_tags);     // (LAMSA_HP_TAG_SUMMARY: at least 4 + (15 + PH_REG_WORDS) * HP_REC_MAX, hp_align.h)
     OutBuf &o = fl->o; o.n = 0; o.cap = out_cap;
     o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);
     r.rc_read = (uint8_t *)arena_alloc(cx, (size_t)r.L + 16);
@@ -268,7 +268,7 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
     int32_t *ev = tags ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)line_ev_cap(r.L)) : nullptr;        // the line's mismatch lists (res_aux)
     int n_reg = 0;
     if (o.w && r.rc_read && la && cur_buf && rec_buf && (ev || !tags)) {
-        la->ev = ev; la->ev_cap = tags ? line_ev_cap(r.L) : 0; la->tags = tags | (a.in.tags & LAMSA_HP_TAG_LEFT_ALIGN);
+        la->ev = ev; la->ev_cap = tags ? line_ev_cap(r.L) : 0; la->tags = all_tags;
         const bool ok = fill_line(r, F, line, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX);
         if (!ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW))) cx.status |= ST_OVERFLOW;
         if (ok) {

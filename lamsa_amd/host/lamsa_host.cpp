@@ -582,7 +582,25 @@ static void merge_batches(Batch &B, std::vector<Batch> &parts, int threads)
 }
 
 // ------------------------------------------------------------------ result stream -> records
-void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm)
+void rec_summary(Rec &r, int read_len)
+{
+    r.ref_span = r.m_bases = r.ins_bases = r.del_bases = r.ins_runs = r.del_runs = 0;
+    for (int32_t w : r.cigar) {
+        const int op = w & 0xf, len = w >> 4;
+        if (cig_aligned(op)) r.m_bases += len;
+        else if (op == 1) { r.ins_bases += len; ++r.ins_runs; }
+        else if (op == 2) { r.del_bases += len; ++r.del_runs; }
+    }
+    r.ref_span = r.m_bases + r.del_bases;
+    r.summed = true;
+    // covered read interval, push_reg_res src/lamsa_aln.c:571-595
+    if (r.cigar.empty()) { r.reg_beg = 1; r.reg_end = read_len; return; }
+    const int32_t c0 = r.cigar.front(), c1 = r.cigar.back();
+    if (r.nstrand == 1) { r.reg_beg = (c0 & 0xf) == 4 ? (c0 >> 4) + 1 : 1; r.reg_end = (c1 & 0xf) == 4 ? read_len - (c1 >> 4) : read_len; }
+    else { r.reg_beg = (c1 & 0xf) == 4 ? (c1 >> 4) + 1 : 1; r.reg_end = (c0 & 0xf) == 4 ? read_len - (c0 >> 4) : read_len; }
+}
+
+void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm, bool summary)
 {
     // (R may hold an earlier read's result: its lines, records and CIGAR vectors are reused, not freed and allocated again)
     R.stage[2].clear();
@@ -597,6 +615,12 @@ void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bo
             ln.rec.resize((size_t)n_res);
             for (Rec &r : ln.rec) {
                 r.offset = (int64_t)(((uint64_t)(uint32_t)s[i + 1] << 32) | (uint32_t)s[i]); r.chr = s[i + 2]; r.nstrand = s[i + 3]; r.score = s[i + 4]; r.NM = s[i + 5];
+                r.summed = false;
+                if (summary) {                                   // LAMSA_HP_TAG_SUMMARY: cigar_n (not kept) and the eight words that stand for the CIGAR
+                    r.reg_beg = s[i + 7]; r.reg_end = s[i + 8]; r.ref_span = s[i + 9]; r.m_bases = s[i + 10]; r.ins_bases = s[i + 11]; r.del_bases = s[i + 12];
+                    r.ins_runs = s[i + 13]; r.del_runs = s[i + 14]; r.summed = true; r.cigar.clear(); r.mm.clear(); i += 15;
+                    continue;
+                }
                 const int cn = s[i + 6]; i += 7;
                 r.cigar.assign(s + i, s + i + cn); i += cn;
                 if (with_mm) { const int nm = s[i]; r.mm.assign(s + i + 1, s + i + 1 + nm); i += 1 + nm; }
@@ -950,6 +974,56 @@ void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index 
     }
 }
 
+// One PAF line from a summed record: the twelve columns, then tp, NM, (AS,) de.  n_mm = NM - inserted - deleted bases (include/lamsa_hp.h).
+static void paf_line(std::string &o, const Rec &r, const Read &rd, const Index &ix, int mapq, bool primary)
+{
+    const int n_mm = r.NM - r.ins_bases - r.del_bases;
+    o += rd.name; o.push_back('\t'); append_int(o, (long long)rd.seq.size()); o.push_back('\t'); append_int(o, r.reg_beg - 1); o.push_back('\t'); append_int(o, r.reg_end);
+    o.push_back('\t'); o.push_back("-+"[r.nstrand]); o.push_back('\t'); o += ix.name[(size_t)r.chr - 1]; o.push_back('\t'); append_int(o, ix.len[(size_t)r.chr - 1]);
+    o.push_back('\t'); append_int(o, (long long)r.offset - 1); o.push_back('\t'); append_int(o, (long long)r.offset - 1 + r.ref_span);
+    o.push_back('\t'); append_int(o, r.m_bases - n_mm); o.push_back('\t'); append_int(o, r.m_bases + r.ins_bases + r.del_bases); o.push_back('\t'); append_int(o, mapq);
+    o += primary ? "\ttp:A:P\tNM:i:" : "\ttp:A:S\tNM:i:"; append_int(o, r.NM);
+    if (primary) { o += "\tAS:i:"; append_int(o, r.score); }
+    const int den = r.m_bases + r.ins_runs + r.del_runs;
+    appendf(o, "\tde:f:%.4f", den > 0 ? (double)(n_mm + r.ins_runs + r.del_runs) / (double)den : 0.0);
+}
+static void append_cg(std::string &o, const Rec &r)
+{
+    static const char OPS[] = "MIDNSHP=XB";
+    o += "\tcg:Z:";
+    const size_t k0 = o.size();
+    o.resize(k0 + 11 * r.cigar.size());
+    char *p = &o[k0];
+    for (int32_t w : r.cigar) { if ((w & 0xf) == 4) continue; p = put_len(p, (unsigned)(w >> 4)); *p++ = OPS[w & 0xf]; }       // (the clips are columns 3 and 4)
+    o.resize((size_t)(p - o.data()));
+}
+
+void write_paf(std::string &o, const ReadResult &R, const Read &rd, const Index &ix, const Options &opt)
+{
+    if (o.capacity() - o.size() < 4096) o.reserve(o.size() + std::max<size_t>(o.size() / 2, 65536));
+    for (int st = 0; st < 3; ++st)
+        for (const Line &la : R.stage[st]) {
+            if (la.merg_x != 1) continue;                       // the lines write_sam prints, in its order
+            for (size_t j = 0; j < la.rec.size(); ++j) {
+                const Rec &r = la.rec[j];
+                paf_line(o, r, rd, ix, (int)la.mapQ, true);
+                if (opt.paf_cg) {
+                    append_cg(o, r);
+                    if (opt.tag_md) { o += "\tMD:Z:"; append_md(o, r, ix); }
+                    if (opt.tag_cs) { o += "\tcs:Z:"; append_cs(o, r, rd, ix); }
+                }
+                o.push_back('\n');
+                if (j == 0)
+                    for (const XaRef &x : la.xa) {               // the alternatives SAM lists in XA:Z: NM and the CIGAR are all it gives them
+                        const Rec &xr = R.stage[x.st][(size_t)x.li].rec[(size_t)x.ri];
+                        paf_line(o, xr, rd, ix, 0, false);
+                        if (opt.paf_cg) append_cg(o, xr);
+                        o.push_back('\n');
+                    }
+            }
+        }
+}
+
 // ------------------------------------------------------------------ seeding front end
 // split_seed (src/lamsa_aln.c:223-303) + lamsa_gem (:1179-1193, gem/gem_map.sh): the read file is cut into overlapping
 // seeds (<reads>.seed, names "<read>_<i>:<offset>"; <reads>.seed.info as the reference writes it) and the GEM mapper is
@@ -1185,10 +1259,15 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     // --left-align: it shifts the gaps before it counts.  Against a library without lamsa_hp_set_result_tags the host shifts the gaps
     // (rec_left_align) and makes the lists (host_mismatches) and the =/X form (rec_to_eqx) itself, in that order.
     const bool need_mm = opt.tag_md || opt.tag_cs;
-    const int dev_tags = lamsa_hp_set_result_tags != nullptr ? (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) | (opt.left_align ? LAMSA_HP_TAG_LEFT_ALIGN : 0) : 0;
+    // --paf: every handle ships a record's 15-word summary in place of its CIGAR (--left-align changes no word of it and is not passed on);
+    // without lamsa_hp_set_result_tags, under --paf-cg and for the stage-4 records the summaries are made from the CIGARs (rec_summary).
+    const bool paf_any = opt.paf || opt.paf_cg;
+    const int dev_tags = lamsa_hp_set_result_tags == nullptr ? 0 : opt.paf ? LAMSA_HP_TAG_SUMMARY :
+                         (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) | (opt.left_align ? LAMSA_HP_TAG_LEFT_ALIGN : 0);
+    const bool dev_sum = (dev_tags & LAMSA_HP_TAG_SUMMARY) != 0;
     const bool dev_mm = (dev_tags & LAMSA_HP_TAG_MISMATCHES) != 0;
     const bool host_mm = (need_mm || opt.tag_eqx) && lamsa_hp_set_result_tags == nullptr, host_eqx = opt.tag_eqx && !(dev_tags & LAMSA_HP_TAG_EQX);
-    const bool host_la = opt.left_align && !(dev_tags & LAMSA_HP_TAG_LEFT_ALIGN);           // --left-align without the device item: rec_left_align, before the lists and the =/X form
+    const bool host_la = opt.left_align && !opt.paf && !(dev_tags & LAMSA_HP_TAG_LEFT_ALIGN);           // --left-align without the device item: rec_left_align, before the lists and the =/X form
     for (lamsa_hp_handle *hh : hs) {
         if (!dev_tags) break;
         const int e = lamsa_hp_set_result_tags(hh, dev_tags);
@@ -1205,7 +1284,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     const double load_s = now_s() - t_begin;
     std::string sam;
     sam_header(sam, ix, pg_line);
-    if (opt.shard_i == 0) fwrite(sam.data(), 1, sam.size(), out);
+    if (opt.shard_i == 0 && !paf_any) fwrite(sam.data(), 1, sam.size(), out);              // (PAF has no header)
     long n_reads = 0, n_bases = 0, n_bad = 0; double kernel_ms = 0;
     const int threads = opt.n_thread > 0 ? opt.n_thread : 1;
     bool eof = false; int ret = 0;
@@ -1427,7 +1506,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             for (int r = r0; r < r1; ++r) {
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
-                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm);
+                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm, dev_sum);
                 if (host_la && R.status == 0) reads_left_align(R, codes + roff[r], L, ix);
                 if (host_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
                 if (host_eqx && R.status == 0) for (int st = 0; st < 2; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) rec_to_eqx(x);
@@ -1470,7 +1549,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
                 if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) {
-                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp, opt.left_align != 0);      // stage-4 records: always shifted on the host, before their rec_aux
+                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp, opt.left_align != 0 && !opt.paf);      // stage-4 records: always shifted on the host, before their rec_aux (--paf: no word of a summary would change)
                     if (opt.tag_eqx) for (Line &ln : R.stage[2]) for (Rec &x : ln.rec) rec_to_eqx(x);       // stage-4 records are made on the host, with their lists (rec_aux)
                 }
                 if (R.status != 0) {
@@ -1479,7 +1558,11 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                     for (int st = 0; st < 3; ++st) R.stage[st].clear();
                 }
                 rank_results(R, L, P);
-                write_sam(o, R, B.reads[(size_t)r], ix, opt);
+                if (paf_any) {
+                    for (int st = 0; st < 3; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) if (!x.summed) rec_summary(x, L);
+                    write_paf(o, R, B.reads[(size_t)r], ix, opt);
+                }
+                else write_sam(o, R, B.reads[(size_t)r], ix, opt);
             }
         });
         // The chunk's text (15 KB per 10-kbp read) goes out in input order.  Into a regular file every thread writes its own part at its own

@@ -64,13 +64,20 @@ struct Batch {                       // the arrays of lamsa_hp_batch, host side
 // cigar: M form, or with --eqx the =/X form (ops 7 / 8): every routine that walks it takes 0, 7 and 8 alike, as read and reference bases
 inline bool cig_aligned(int op) { return op == 0 || op == 7 || op == 8; }      // M, =, X: read and reference bases facing each other
 struct Rec { int64_t offset = 0; int chr = 0, nstrand = 0, score = 0, NM = 0, reg_beg = 0, reg_end = 0; std::vector<int32_t> cigar;   // res_t
-             std::vector<int32_t> mm; };     // --MD, --cs: the mismatches, ref_off << 2 | base (include/lamsa_hp.h, LAMSA_HP_TAG_MISMATCHES)
+             std::vector<int32_t> mm;        // --MD, --cs: the mismatches, ref_off << 2 | base (include/lamsa_hp.h, LAMSA_HP_TAG_MISMATCHES)
+             // --paf, --paf-cg: the record's summary (LAMSA_HP_TAG_SUMMARY, include/lamsa_hp.h; q_beg / q_end are reg_beg / reg_end), from the
+             // stream's 15-word record -- the CIGAR is empty then -- or from the CIGAR (rec_summary); summed: the six are set
+             bool summed = false; int ref_span = 0, m_bases = 0, ins_bases = 0, del_bases = 0, ins_runs = 0, del_runs = 0; };
 struct XaRef { int st, li, ri; };
 struct Line { int line_score = 0, tol_score = 0, tol_NM = 0, merg_x = 0, merg_y = 0; uint8_t mapQ = 0; std::vector<Rec> rec; std::vector<XaRef> xa; };   // line_aln_res
 struct ReadResult { int status = 0; std::vector<Line> stage[3]; };   // aln_res[3]: first round, remain round, BWT rescue (empty)
 
 // with_mm: the stream carries the records' mismatch lists (lamsa_hp_set_result_tags(h, LAMSA_HP_TAG_MISMATCHES))
-void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm = false);
+// summary: the records are the 15 words of LAMSA_HP_TAG_SUMMARY (no CIGAR, no list)
+void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm = false, bool summary = false);
+// the eight summary words of include/lamsa_hp.h (LAMSA_HP_TAG_SUMMARY) from the record's CIGAR, ops 0, 7 and 8 alike: reg_beg, reg_end and the
+// six fields behind `summed`.  For --paf-cg, for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host
+void rec_summary(Rec &r, int read_len);
 void rank_results(ReadResult &R, int read_len, const lamsa_hp_para &P);
 // the record's CIGAR into =/X form from its mismatch list, to the definition of include/lamsa_hp.h (what the device does under
 // LAMSA_HP_TAG_EQX): for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host
@@ -98,6 +105,7 @@ struct Options {
     int parse_only = 0;                                   // --parse-only: read and parse the inputs, no GPU work, no output (ingest timing)
     int tag_md = 0, tag_sa = 0;                           // --MD, --SA: MD:Z / SA:Z at the end of every mapped record (not in the reference's output)
     int tag_eqx = 0, tag_cs = 0;                          // --eqx: every printed CIGAR in =/X form (LAMSA_HP_TAG_EQX, include/lamsa_hp.h); --cs: cs:Z (short form) on every mapped record
+    int paf = 0, paf_cg = 0;                              // --paf: PAF lines from the per-record summaries of the GPU (LAMSA_HP_TAG_SUMMARY); --paf-cg: PAF with cg:Z from the ordinary stream
     int left_align = 0;                                   // --left-align: the gaps of every printed CIGAR shifted as far left as they go (LAMSA_HP_TAG_LEFT_ALIGN, include/lamsa_hp.h)
     float ed_rate = -1, mis_rate = -1, mat_rate = -1;     // -e, -x; defaults per read type (src/lamsa_aln.h:26-70)
     std::string gem_dir;                                  // directory holding gem-mapper (default: <directory of this binary>/gem)
@@ -108,6 +116,8 @@ struct Stats { long n_reads = 0, n_bases = 0, n_bad = 0; double kernel_ms = 0;
 
 void sam_header(std::string &o, const Index &ix, const std::string &pg);
 void write_sam(std::string &o, const ReadResult &R, const Read &rd, const Index &ix, const Options &opt);
+// PAF lines of the records write_sam would print, in its order, every XA:Z alternative as a line of its own behind its record; every record summed
+void write_paf(std::string &o, const ReadResult &R, const Read &rd, const Index &ix, const Options &opt);
 int run_seeding(const Options &opt, const lamsa_hp_para &P, long *pid = nullptr);   // pid: leave the mapper running and return its process id
 int run_index(const std::string &fasta, const std::string &gem_dir, bool with_gem, bool from_pac = false);      // index.cpp
 int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::string &pg_line, Stats *stats);

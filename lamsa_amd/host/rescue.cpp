@@ -130,7 +130,7 @@ void collect_regs(const ReadResult &R, std::vector<Reg> &regs)
             for (const Rec &r : la.rec) {
                 Reg g; g.beg = r.reg_beg; g.end = r.reg_end;
                 RegB b, e; b.chr = e.chr = r.chr; b.is_rev = e.is_rev = 1 - r.nstrand;
-                const int64_t last = r.offset + ref_in_cigar(r.cigar) - 1;
+                const int64_t last = r.offset + (r.cigar.empty() && r.summed ? r.ref_span : ref_in_cigar(r.cigar)) - 1;     // (LAMSA_HP_TAG_SUMMARY: the span comes with the record)
                 if (r.nstrand == 1) { b.pos = r.offset; e.pos = last; } else { e.pos = r.offset; b.pos = last; }
                 g.rb.push_back(b); g.re.push_back(e);
                 regs.push_back(std::move(g));

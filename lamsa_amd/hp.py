@@ -63,6 +63,7 @@ EXPORTS = ("lamsa_hp_para_init", "lamsa_hp_para_finish", "lamsa_hp_create", "lam
 TAG_MISMATCHES = 1      # LAMSA_HP_TAG_MISMATCHES: every record of the result stream also lists its mismatches
 TAG_EQX = 2             # LAMSA_HP_TAG_EQX: the CIGARs of the result stream are in =/X form (every M split into '=' 7 and 'X' 8 pieces)
 TAG_LEFT_ALIGN = 8      # LAMSA_HP_TAG_LEFT_ALIGN: every gap with an M on either side is shifted as far left as it goes (include/lamsa_hp.h)
+TAG_SUMMARY = 32        # LAMSA_HP_TAG_SUMMARY: every record is 15 words, eight summary words in place of its CIGAR (include/lamsa_hp.h); not with 1 or 2
 
 _lib = None
 
@@ -193,7 +194,10 @@ class LamsaHp:
         n_mm and n_mm words ref_off << 2 | base; TAG_EQX: cigar_n and the CIGAR words of every record are the =/X form, each M
         element split into its '=' (op 7) and 'X' (op 8) pieces, every other word unchanged; both may be set, the lists are in
         the stream only with TAG_MISMATCHES; TAG_LEFT_ALIGN: the gaps of every CIGAR are left-aligned, which changes M lengths only,
-        and the other two items describe the shifted alignment); 0 = none, the default.  Raises while batches are in flight."""
+        and the other two items describe the shifted alignment; TAG_SUMMARY: every record is the 15 words offset_lo, offset_hi, chr,
+        nstrand, score, NM, cigar_n, q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs and no CIGAR word --
+        refused with TAG_MISMATCHES or TAG_EQX, and with TAG_LEFT_ALIGN the same words as alone); 0 = none, the default.  Raises
+        while batches are in flight."""
         rc = self.L.lamsa_hp_set_result_tags(self._h, int(flags))
         if rc != 0:
             raise RuntimeError("lamsa_hp_set_result_tags failed: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
