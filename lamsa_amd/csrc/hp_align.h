@@ -2,8 +2,7 @@
 // second round (2')/(3') on the uncovered read regions -- the body of the reference's per-read
 // worker lamsa_main_aln (src/lamsa_aln.c:857-871), minus stage (4)/(5)/(6) which stay on the host.
 #pragma once
-#include "hp_fill.h"
-#include "hp_eqx.h"
+#include "hp_out.h"
 #include "hp_sort.h"
 
 namespace hp {
@@ -64,109 +63,16 @@ HP_NOINL void regs_remain(ReadCtx &r, Regs &G, int min_thd, int max_thd)
     }
 }
 
-// ---- result stream (hp_batch.h) ----
-struct OutBuf { int32_t *w; int n, cap; };
-HP_INL void out_put(Ctx &cx, OutBuf &o, int32_t v) { if (o.n < o.cap) o.w[o.n++] = v; else cx.status |= ST_OVERFLOW; }
-
-enum { HP_SUMREC_WORDS = 15 };   // a record under LAMSA_HP_TAG_SUMMARY: the 7 header words and the 8 of Rec::sum (include/lamsa_hp.h)
-HP_FN void out_line(Ctx &cx, OutBuf &o, const LineRes &la)
-{
-    out_put(cx, o, la.line_score); out_put(cx, o, la.tol_score); out_put(cx, o, la.tol_NM); out_put(cx, o, la.cur_res_n + 1);
-    for (int j = 0; j <= la.cur_res_n; ++j) {
-        const Rec &rec = la.rec[j];
-        if (la.tags & LAMSA_HP_TAG_SUMMARY) {                         // the record's 15 words, one per lane, in one store; its CIGAR stays where it is
-            if (o.n + HP_SUMREC_WORDS <= o.cap) {
-                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
-                const HP_G int32_t *sum = (const HP_G int32_t *)rec.sum;      // (written by every lane in res_aux: a lane reads its own store)
-                const int32_t lo = (int32_t)(rec.offset & 0xffffffffll), hi = (int32_t)(rec.offset >> 32);
-                WAVE_FOR(l) {
-                    int32_t v = l >= 7 && l < HP_SUMREC_WORDS ? sum[l - 7] : 0;
-                    v = l == 0 ? lo : l == 1 ? hi : l == 2 ? rec.chr : l == 3 ? rec.nstrand : l == 4 ? rec.score : l == 5 ? rec.NM : l == 6 ? rec.cig.n : v;
-                    if (l < HP_SUMREC_WORDS) dst[l] = v;
-                }
-                o.n += HP_SUMREC_WORDS;
-                wv::sync();
-            }
-            else cx.status |= ST_OVERFLOW;
-            continue;
-        }
-        out_put(cx, o, (int32_t)(rec.offset & 0xffffffffll)); out_put(cx, o, (int32_t)(rec.offset >> 32));
-        out_put(cx, o, rec.chr); out_put(cx, o, rec.nstrand); out_put(cx, o, rec.score); out_put(cx, o, rec.NM);
-        if (la.tags & LAMSA_HP_TAG_EQX) {                             // the CIGAR in =/X form (hp_eqx.h): cigar_n is known once the words are written
-            const int n = o.n < o.cap ? eqx_words(rec.cig.c, rec.cig.n, rec.mm, rec.n_mm, o.w + o.n + 1, o.cap - o.n - 1) : -1;
-            if (n >= 0) { o.w[o.n] = n; o.n += 1 + n; }
-            else cx.status |= ST_OVERFLOW;
-        }
-        else {
-            out_put(cx, o, rec.cig.n);
-            if (o.n + rec.cig.n <= o.cap) {                           // the record's CIGAR, copied by the lanes (word by word it was 2 500 dependent trips per line: 14 % of the fill kernel)
-                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
-                const HP_G cig_t *src = (const HP_G cig_t *)rec.cig.c;
-                const int cn = rec.cig.n;
-                wv::sync();
-                for (int b0 = 0; b0 < cn; b0 += 64) { WAVE_FOR(l) { const int k = b0 + l; if (k < cn) dst[k] = (int32_t)src[k]; } }
-                o.n += cn;
-                wv::sync();
-            }
-            else cx.status |= ST_OVERFLOW;
-        }
-        if (la.tags & LAMSA_HP_TAG_MISMATCHES) {                      // the record's mismatch list (res_aux)
-            const int nm = rec.n_mm;
-            out_put(cx, o, nm);
-            if (o.n + nm <= o.cap) {
-                HP_G int32_t *dst = (HP_G int32_t *)(o.w + o.n);
-                const HP_G int32_t *src = (const HP_G int32_t *)rec.mm;
-                wv::sync();
-                for (int b0 = 0; b0 < nm; b0 += 64) { WAVE_FOR(l) { const int k = b0 + l; if (k < nm) dst[k] = src[k]; } }
-                o.n += nm;
-                wv::sync();
-            }
-            else cx.status |= ST_OVERFLOW;
-        }
-    }
-}
-
-// The mismatch lists of a line (LineRes::ev, made under either item of HP_TAGS_LISTS) -- at most one per aligned read base, the records of a
-// line cover disjoint parts of the read -- and what the items add to the line's result words: LAMSA_HP_TAG_MISMATCHES the lists and a
-// count per record, LAMSA_HP_TAG_EQX at most two words per mismatch (a record has at most cigar_n + 2 n_mm words, hp_eqx.h)
-// LAMSA_HP_TAG_LEFT_ALIGN adds no word and needs no list.
-// LAMSA_HP_TAG_SUMMARY: a record is HP_SUMREC_WORDS words whatever its CIGAR holds, so a line of the phased fill is at most
-// 4 + 15 * HP_REC_MAX words and the PH_REG_WORDS * HP_REC_MAX of its covered intervals: line_sum_words on top of the flag-off capacity holds
-// that for every read length, a read of a few bases included (12 L alone does not).  On the one-kernel path and in the batch's stream the term
-// in L stays as it is (the buffers do not shrink under the item): it pays the 8 words that stand for a CIGAR wherever the CIGARs of the read's
-// records have 8 elements on average, and read_sum_words per read (times the scale) pays them for a full line of HP_REC_MAX records of
-// fewer elements.  A read with more such records than that is short of words as any other: ST_OVERFLOW, the second pass.
-enum { HP_TAGS_LISTS = LAMSA_HP_TAG_MISMATCHES | LAMSA_HP_TAG_EQX };
-// the items as the fill applies them: under LAMSA_HP_TAG_SUMMARY no CIGAR is shipped and left alignment changes M lengths only -- not a word
-// of a summary (include/lamsa_hp.h) -- so the shift is skipped; the item never comes with a list item (lamsa_hp_set_result_tags)
-HP_HD int fill_tags(int t) { return (t & LAMSA_HP_TAG_SUMMARY) ? LAMSA_HP_TAG_SUMMARY : t & (HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN); }
-// what lamsa_hp_set_result_tags accepts: the four items, LAMSA_HP_TAG_SUMMARY with neither item of HP_TAGS_LISTS (nothing to list or split)
-HP_HD bool result_tags_valid(int t) { return !(t & ~(HP_TAGS_LISTS | LAMSA_HP_TAG_LEFT_ALIGN | LAMSA_HP_TAG_SUMMARY)) && !((t & LAMSA_HP_TAG_SUMMARY) && (t & HP_TAGS_LISTS)); }
-HP_INL int line_ev_cap(int L) { return L + 64; }
-HP_INL int line_ev_words(int L) { return L + 64 + HP_REC_MAX; }
-HP_INL int line_eqx_words(int L) { return 2 * (L + 64); }
-HP_HD int line_sum_words() { return HP_SUMREC_WORDS * HP_REC_MAX; }
-HP_HD int read_sum_words() { return 8 * HP_REC_MAX; }
-HP_INL int line_tag_words(int L, int tags) { return ((tags & LAMSA_HP_TAG_MISMATCHES) ? line_ev_words(L) : 0) + ((tags & LAMSA_HP_TAG_EQX) ? line_eqx_words(L) : 0) + ((tags & LAMSA_HP_TAG_SUMMARY) ? line_sum_words() : 0); }
-// words of a read's result stream on the one-kernel path (align_read); the second pass sizes its arena by it
-HP_HD int64_t read_out_cap(int L, int scale, int tags) { return 64 + (12LL * L + ((tags & LAMSA_HP_TAG_MISMATCHES) ? 4LL * L + 4 * HP_REC_MAX : 0) + ((tags & LAMSA_HP_TAG_EQX) ? 8LL * L + 512 : 0) + ((tags & LAMSA_HP_TAG_SUMMARY) ? read_sum_words() : 0)) * scale; }
-
 // frag_check over all lines of one round (frag_check.c:886-955) + get_reg (lamsa_aln.c:597) for round 1
 HP_NOINL void fill_round(ReadCtx &r, const FLines &F, OutBuf &o, Regs *G, int reg_cap, int scale, int tags)
 {
     Ctx &cx = r.cx;
     const size_t mark = arena_mark(cx.tmp);
-    const int cur_cap = (2 * r.L + 512) * scale;
-    LineRes *la = (LineRes *)arena_alloc(cx, sizeof(LineRes));
-    cig_t *cur_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)cur_cap);
-    cig_t *rec_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)(cur_cap + 4 * HP_REC_MAX));
-    const bool lists = (tags & HP_TAGS_LISTS) != 0;
-    const int ev_cap = lists ? line_ev_cap(r.L) * scale : 0;
-    int32_t *ev = lists ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)ev_cap) : nullptr;
-    if (!la || !cur_buf || !rec_buf || (lists && !ev)) { arena_release(cx.tmp, mark); return; }
-    la->ev = ev; la->ev_cap = ev_cap; la->tags = tags;
+    const LineBufs b = line_bufs(cx, r.L, scale, tags);
+    LineRes *la = b.la;
+    if (!la) { arena_release(cx.tmp, mark); return; }
     for (int j = 0; j < F.n; ++j) {
-        if (!fill_line(r, F, j, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX)) break;
+        if (!fill_line(r, F, j, *la, b.cur_buf, b.cur_cap, b.rec_buf, b.rec_cap)) break;
         out_line(cx, o, *la);
         if (G && la->tol_score >= 0) for (int k = 0; k <= la->cur_res_n; ++k) regs_push(r, *G, reg_cap, la->rec[k]);
     }
@@ -337,7 +243,7 @@ HP_NOINL void align_read(const AlignArgs &a, int rd, int wave_slot, HP_L int32_t
         else {
             o.w[0] = st;
             wv::sync();
-            for (int b = 0; b < n_words; b += 64) { WAVE_FOR(l) { const int i = b + l; if (i < n_words) dst[i] = o.w[i]; } }
+            out_copy((HP_G int32_t *)dst, (const HP_G int32_t *)o.w, n_words);
         }
         a.out.read_out_off[rd] = (int64_t)off; a.out.read_out_len[rd] = n_words;
     } else { a.out.read_out_off[rd] = -1; a.out.read_out_len[rd] = 0; }

@@ -340,22 +340,6 @@ static int grow(lamsa_hp_handle *h, DevBuf &b, size_t bytes)
     return b.ensure(bytes);
 }
 
-// result + CIGAR bytes per read base of a wave's scratch; `eqx`: what the =/X words of LAMSA_HP_TAG_EQX add (a line's: 2 words per base,
-// line_eqx_words; a read's on the one-kernel path: 8, read_out_cap)
-static size_t tag_slab_per_base(int tags, int eqx) { return (size_t)((tags & HP_TAGS_LISTS) ? 152 : 128) + ((tags & LAMSA_HP_TAG_EQX) ? (size_t)eqx : 0); }
-// LAMSA_HP_TAG_SUMMARY costs nothing per base.  Per wave it adds the words its capacities add to the result buffers (hp_align.h): a line's
-// line_sum_words on the phased fill, read_sum_words times the scale on the one-kernel path.  (Rec::sum, 8 words in each of a LineRes's
-// HP_REC_MAX records with or without the item, is 2 KiB of the slabs' constant 256 KiB, of which the fixed-size records took under 16.)
-static size_t tag_slab_fixed(int tags, int scale, bool phased) { return (tags & LAMSA_HP_TAG_SUMMARY) ? sizeof(int32_t) * (size_t)(phased ? line_sum_words() : read_sum_words() * scale) : 0; }
-static size_t slab_bytes_for(const lamsa_hp_para &P, int L, int H, int scale, int tags)
-{   // per-wave scratch: node arrays, sort index + line sets (~424 B/hit), result + CIGAR buffers (~128 B/base; 24 more with the
-    // mismatch lists of LAMSA_HP_TAG_MISMATCHES or LAMSA_HP_TAG_EQX, 40 more for the =/X words of LAMSA_HP_TAG_EQX: read_out_cap), and the direction matrix
-    // of the largest extension: (2w+1) columns x (L + 2*hash_step) rows.
-    // Reads that need more flag LAMSA_HP_ST_OVERFLOW and are re-run by the retry pass with `scale` = 8.
-    const size_t z = (2 * (size_t)P.band_w + 128) * ((size_t)L + 256);
-    return al256(((size_t)256 << 10) + tag_slab_fixed(tags, scale, false) + (size_t)scale * tag_slab_per_base(tags, 40) * (size_t)L + 424 * (size_t)H + z * (size_t)(scale > 1 ? 4 : 1));
-}
-
 // validate `B`, build its processing order and sort index, copy it into slot `T` on the copy stream
 
 static int upload_into(lamsa_hp_handle *h, Slot *S, const lamsa_hp_batch *B)
@@ -573,14 +557,6 @@ static PhasedLayout phased_layout(int n, int64_t n_hits, int64_t n_bases, int64_
     Y.bytes = off;
     return Y;
 }
-// words of a batch's result stream; the mismatch lists (LAMSA_HP_TAG_MISMATCHES) are at most one word per aligned base and a count per record,
-// the =/X pieces (LAMSA_HP_TAG_EQX) at most two words per aligned base.  LAMSA_HP_TAG_SUMMARY: 8 words per record stand for its CIGAR; the 4
-// words per base stay and pay them as they paid the CIGARs, and read_sum_words per read pays them for a full line of short records (hp_align.h)
-static int64_t main_stream_cap(int n, int64_t n_bases, int tags)
-{
-    return 1024 + (int64_t)n * 256 + 4 * n_bases + ((tags & LAMSA_HP_TAG_MISMATCHES) ? (int64_t)n * 128 + 2 * n_bases : 0) + ((tags & LAMSA_HP_TAG_EQX) ? (int64_t)n * 128 + 4 * n_bases : 0) +
-           ((tags & LAMSA_HP_TAG_SUMMARY) ? (int64_t)n * read_sum_words() : 0);
-}
 
 // The main pass of the batch in slot `T` as the five launches of hp_phase.h, with the launch resources of slot `Ln`.
 // scratch of a wave of each kind of launch (all launches of a batch share one allocation, one after the other): the chaining launches keep
@@ -612,12 +588,12 @@ static SlabPlan slab_plan(lamsa_hp_handle *h, int max_L, int max_H, bool shared 
     // itself, a lane-DP group's buffers.  Wave jobs: an ordinary slab takes the junctions and the end extensions of a few thousand rows; the
     // direction matrix of the longest end extension (the whole read long) lives in one of the big slabs that only the first waves own.
     Q.chain = al256(((size_t)256 << 10) + 128 * (size_t)max_L + 424 * (size_t)max_H);
-    Q.fill = al256(((size_t)256 << 10) + tag_slab_fixed(h->result_tags, 1, true) + tag_slab_per_base(h->result_tags, 16) * (size_t)max_L + sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
+    Q.fill = al256(fill_slab_bytes(max_L, h->result_tags, sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64));
     { static const int kb = getenv("LAMSA_HP_WJ_SLAB_KB") ? atoi(getenv("LAMSA_HP_WJ_SLAB_KB")) : 0;    // diagnostic
       Q.wj = ((size_t)(kb > 0 ? kb : 1024) << 10) + 33 * 256; }
     Q.wjb = al256((size_t)wj_need(&P, WJ_HEAD, max_L, max_L + 2 * P.hash_step + 64) + ((size_t)64 << 10)) + 33 * 256;
     if (Q.wjb < Q.wj) Q.wjb = Q.wj;
-    if (g_nowave) Q.fill = std::max(Q.fill, slab_bytes_for(P, max_L, max_H, 1, h->result_tags));            // (diagnostics: the fill runs every DP itself)
+    if (g_nowave) Q.fill = std::max(Q.fill, al256(read_slab_bytes(P.band_w, max_L, max_H, 1, h->result_tags)));            // (diagnostics: the fill runs every DP itself)
     if (h->scratch_limit) { const size_t lim = al256(h->scratch_limit); Q.chain = std::min(Q.chain, lim); Q.fill = std::min(Q.fill, lim); Q.wj = std::min(Q.wj, lim); Q.wjb = std::min(Q.wjb, lim); }
     int pc = 0, pf = 0, pd = 0, pw = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, g_chain_shapes[shape].k1, 64, 0) != hipSuccess || pc < 1) pc = 4 * g_chain_shapes[shape].waves_per_simd;
@@ -717,7 +693,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
 static int launch_align(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, OutDev &O, const int32_t *d_order, int n_units, int scale, int max_L, int max_H,
                         hipEvent_t e0, hipEvent_t e1, bool wait)
 {
-    size_t slab_per_wave = slab_bytes_for(h->para, max_L, max_H, scale, h->result_tags);
+    size_t slab_per_wave = al256(read_slab_bytes(h->para.band_w, max_L, max_H, scale, h->result_tags));
     if (scale == 1 && h->scratch_limit && slab_per_wave > h->scratch_limit) slab_per_wave = al256(h->scratch_limit);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_align_batch, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4;
@@ -768,7 +744,7 @@ static int start_main(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln)
     if (rc) return rc;
     const int n = T.n_reads;
     if (n == 0) return LAMSA_HP_OK;
-    if (Ln.out1.ensure(n, main_stream_cap(n, T.n_bases, h->result_tags))) { h->err = "hipMalloc(out)"; return LAMSA_HP_ENOMEM; }
+    if (Ln.out1.ensure(n, batch_out_cap(n, T.n_bases, h->result_tags))) { h->err = "hipMalloc(out)"; return LAMSA_HP_ENOMEM; }
     Ln.phased = false;
     if (!g_mono) return launch_phased(h, S, T, Ln, Ln.out1, Ln.e0, Ln.e1);
     return launch_align(h, S, T, Ln, Ln.out1, T.d_order, n, 1, T.max_L, T.max_H, Ln.e0, Ln.e1, false);
@@ -964,7 +940,7 @@ extern "C" int lamsa_hp_reserve(lamsa_hp_handle *h, int32_t n_reads, int64_t n_b
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight"; return LAMSA_HP_EINVAL; }
     const SlabPlan Q = slab_plan(h, max_read_len, max_hits_per_read, false, chain_shape(h->para, n_reads, n_bases));
-    const int64_t cap = main_stream_cap(n_reads, n_bases, h->result_tags);
+    const int64_t cap = batch_out_cap(n_reads, n_bases, h->result_tags);
     const PhasedLayout Y = phased_layout(n_reads, n_hits, n_bases, cap);
     // the packed input of a batch (upload_into): every array plus its 256-byte alignment, both CIGAR forms' staging included
     const size_t in_bytes = (size_t)n_bases + 16 * (size_t)n_reads * 4 + 32 * ((size_t)n_hits + n_reads) + 8 * (size_t)n_hits + 5 * (size_t)n_cig + 64 * 256 + 4096;

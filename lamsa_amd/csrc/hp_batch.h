@@ -48,7 +48,7 @@ struct BatchIn {
 //              it counts): some M lengths differ, and with them the offsets of the lists and the =/X pieces; no word is added or dropped
 //              [in.tags & LAMSA_HP_TAG_SUMMARY] no cigar words: cigar_n (of the M form) is followed by the eight words of Rec::sum (res_aux) --
 //              q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs -- so a record is 15 words, written by out_line with one
-//              store of 15 lanes; never together with the two items above it, and LAMSA_HP_TAG_LEFT_ALIGN is ignored (fill_tags, hp_align.h)
+//              store of 15 lanes; never together with the two items above it, and LAMSA_HP_TAG_LEFT_ALIGN is ignored (fill_tags, hp_out.h)
 struct BatchOut {
     int32_t *stream;             // global result arena
     int64_t stream_cap;          // words

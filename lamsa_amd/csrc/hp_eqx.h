@@ -1,4 +1,4 @@
-// hp_eqx.h -- LAMSA_HP_TAG_EQX: a record's CIGAR in =/X form, written straight into the result words (out_line, hp_align.h).
+// hp_eqx.h -- LAMSA_HP_TAG_EQX: a record's CIGAR in =/X form, written straight into the result words (out_line, hp_out.h).
 //
 // Every M element is replaced by its pieces -- maximal runs of aligned bases that equal the reference ('=', op 7) or differ from it
 // ('X', op 8; a read N differs, as for NM) -- and every other element is copied.  Pieces never merge across elements.  The inputs are

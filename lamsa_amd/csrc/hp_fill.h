@@ -28,7 +28,7 @@ struct Rec {                     // res_t, frag_check.h:46-59
     int64_t offset, refend; int32_t chr, nstrand, readend, score, NM; CigV cig;
     int32_t *mm; int32_t n_mm;   // with LineRes::ev: the record's mismatches (ref_off << 2 | base), a view into ev like the CIGARs
     int32_t sum[8];              // set by res_aux from what it counts anyway: q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs
-                                 // (the last eight words of a record under LAMSA_HP_TAG_SUMMARY, include/lamsa_hp.h; out_line, hp_align.h)
+                                 // (the last eight words of a record under LAMSA_HP_TAG_SUMMARY, include/lamsa_hp.h; out_line, hp_out.h)
 };
 struct LineRes {                 // line_aln_res, frag_check.h:61-73
     int line_score, tol_score, tol_NM, cur_res_n;

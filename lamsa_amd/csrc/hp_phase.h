@@ -37,12 +37,12 @@ struct RdMeta {                  // 72 bytes per read, zeroed before chain1
 
 struct UnitRec {                 // one line to fill
     int32_t read, line;
-    int64_t out_off;             // its serialised result in the line arena (words): out_line words, then 10 words per region
+    int64_t out_off;             // its serialised result in the line arena (words): out_line words, then PH_REG_WORDS per region (out_reg, hp_out.h)
     int32_t out_len, n_reg;
     int32_t pad[2];
 };
 
-enum { PH_NBUCKET = 8, PH_REG_WORDS = 10 };
+enum { PH_NBUCKET = 8 };
 
 // Laid out by 128-byte lines: a line that thousands of waves update with atomics must not also hold words the same waves READ once per
 // job -- every such read then queues behind the atomics in the one L2 channel that owns the line.  (Round 4: wj_bytes / wj_cells shared a
@@ -256,20 +256,15 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
     F.n = M.fl_n[round]; F.nfrag = M.fl_nfrag[round];
     flines_bind(F, a.fl_base + M.fl_off[round], F.n, M.fl_tot[round]);
     F.jarena = a.job_base;
-    const int cur_cap = 2 * r.L + 512;
-    const int all_tags = fill_tags(a.in.tags), tags = all_tags & HP_TAGS_LISTS;          // either item of HP_TAGS_LISTS needs the line's mismatch lists
-    const int out_cap = 64 + 12 * r.L + PH_REG_WORDS * HP_REC_MAX + line_tag_words(r.L, all_tags);     // (LAMSA_HP_TAG_SUMMARY: at least 4 + (15 + PH_REG_WORDS) * HP_REC_MAX, hp_align.h)
-    OutBuf &o = fl->o; o.n = 0; o.cap = out_cap;
-    o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)out_cap);
+    const int tags = fill_tags(a.in.tags);
+    OutBuf &o = fl->o; o.n = 0; o.cap = line_out_cap(r.L, tags);
+    o.w = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)o.cap);
     r.rc_read = (uint8_t *)arena_alloc(cx, (size_t)r.L + 16);
-    LineRes *la = (LineRes *)arena_alloc(cx, sizeof(LineRes));
-    cig_t *cur_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)cur_cap);
-    cig_t *rec_buf = (cig_t *)arena_alloc(cx, sizeof(cig_t) * (size_t)(cur_cap + 4 * HP_REC_MAX));
-    int32_t *ev = tags ? (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)line_ev_cap(r.L)) : nullptr;        // the line's mismatch lists (res_aux)
+    const LineBufs b = line_bufs(cx, r.L, 1, tags);
+    LineRes *la = b.la;
     int n_reg = 0;
-    if (o.w && r.rc_read && la && cur_buf && rec_buf && (ev || !tags)) {
-        la->ev = ev; la->ev_cap = tags ? line_ev_cap(r.L) : 0; la->tags = all_tags;
-        const bool ok = fill_line(r, F, line, *la, cur_buf, cur_cap, rec_buf, cur_cap + 4 * HP_REC_MAX);
+    if (o.w && r.rc_read && la) {
+        const bool ok = fill_line(r, F, line, *la, b.cur_buf, b.cur_cap, b.rec_buf, b.rec_cap);
         if (!ok && !(cx.status & (ST_REFEXIT | ST_OVERFLOW))) cx.status |= ST_OVERFLOW;
         if (ok) {
             out_line(cx, o, *la);
@@ -280,11 +275,7 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
                 G.rb = (RegB *)arena_alloc(cx, sizeof(RegB) * 2 * HP_REC_MAX); G.re = G.rb ? G.rb + HP_REC_MAX : nullptr;
                 if (G.beg && G.rb) {
                     for (int k = 0; k <= la->cur_res_n; ++k) regs_push(r, G, HP_REC_MAX, la->rec[k]);
-                    for (int k = 0; k < G.n; ++k) {
-                        out_put(cx, o, G.beg[k]); out_put(cx, o, G.end[k]);
-                        out_put(cx, o, G.rb[k].is_rev); out_put(cx, o, G.rb[k].chr); out_put(cx, o, (int32_t)(G.rb[k].pos & 0xffffffffll)); out_put(cx, o, (int32_t)(G.rb[k].pos >> 32));
-                        out_put(cx, o, G.re[k].is_rev); out_put(cx, o, G.re[k].chr); out_put(cx, o, (int32_t)(G.re[k].pos & 0xffffffffll)); out_put(cx, o, (int32_t)(G.re[k].pos >> 32));
-                    }
+                    for (int k = 0; k < G.n; ++k) out_reg(cx, o, G, k);
                     n_reg = G.n;
                 }
                 arena_release(cx.tmp, mark);
@@ -296,10 +287,8 @@ HP_NOINL void phase_fill(const PhaseArgs &a, int round, int u, int wave_slot, HP
         if (wv::leader()) off = atomicAdd(&a.ctl->line_cursor, (unsigned long long)o.n);
         off = (unsigned long long)wv::uni64((long long)off);
         if ((int64_t)(off + (unsigned long long)o.n) <= a.line_cap) {
-            HP_G int32_t *dst = (HP_G int32_t *)(a.line_base + off);
-            const HP_G int32_t *src = (const HP_G int32_t *)o.w;
             wv::sync();
-            for (int b = 0; b < o.n; b += 64) { WAVE_FOR(l) { const int i = b + l; if (i < o.n) dst[i] = src[i]; } }
+            out_copy((HP_G int32_t *)(a.line_base + off), (const HP_G int32_t *)o.w, o.n);
             U.out_off = (int64_t)off; U.out_len = o.n; U.n_reg = n_reg;
         } else cx.status |= ST_OVERFLOW;
     }
@@ -657,10 +646,7 @@ HP_NOINL void phase_chain2(const PhaseArgs &a, int rd, int wave_slot, HP_L int32
             const int32_t *w = a.line_base + U.out_off + (U.out_len - PH_REG_WORDS * U.n_reg);
             for (int k = 0; k < U.n_reg; ++k, w += PH_REG_WORDS) {
                 if (G.n >= reg_cap) { cx.status |= ST_OVERFLOW; break; }
-                const int g = G.n++;
-                G.beg[g] = w[0]; G.end[g] = w[1];
-                G.rb[g].is_rev = w[2]; G.rb[g].chr = w[3]; G.rb[g].pos = (int64_t)(((unsigned long long)(unsigned)w[5] << 32) | (unsigned)w[4]);
-                G.re[g].is_rev = w[6]; G.re[g].chr = w[7]; G.re[g].pos = (int64_t)(((unsigned long long)(unsigned)w[9] << 32) | (unsigned)w[8]);
+                reg_read(w, G, G.n++);
             }
         }
         wv::sync();
@@ -705,8 +691,7 @@ HP_NOINL void phase_publish(const PhaseArgs &a, int rd)
                 for (int j = 0; j < M.fl_n[round]; ++j) {
                     const UnitRec &U = a.units[(size_t)round * a.unit_cap + M.unit_base[round] + j];
                     const int n = U.out_len - PH_REG_WORDS * U.n_reg;
-                    const HP_G int32_t *src = (const HP_G int32_t *)(a.line_base + U.out_off);
-                    for (int b = 0; b < n; b += 64) { WAVE_FOR(l) { const int i = b + l; if (i < n) dst[at + i] = src[i]; } }
+                    out_copy(dst + at, (const HP_G int32_t *)(a.line_base + U.out_off), n);
                     at += n;
                 }
         a.out.read_out_off[rd] = (int64_t)off; a.out.read_out_len[rd] = n_words;

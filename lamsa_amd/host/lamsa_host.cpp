@@ -582,6 +582,17 @@ static void merge_batches(Batch &B, std::vector<Batch> &parts, int threads)
 }
 
 // ------------------------------------------------------------------ result stream -> records
+// covered read interval of a record, push_reg_res src/lamsa_aln.c:571-595: the read without the record's soft clips, on the forward strand
+void cigar_read_interval(const std::vector<int32_t> &cigar, int nstrand, int read_len, int &beg, int &end)
+{
+    beg = 1; end = read_len;
+    if (cigar.empty()) return;
+    const int32_t c0 = cigar.front(), c1 = cigar.back();
+    const int32_t head = nstrand == 1 ? c0 : c1, tail = nstrand == 1 ? c1 : c0;
+    if ((head & 0xf) == 4) beg = (head >> 4) + 1;
+    if ((tail & 0xf) == 4) end = read_len - (tail >> 4);
+}
+
 void rec_summary(Rec &r, int read_len)
 {
     r.ref_span = r.m_bases = r.ins_bases = r.del_bases = r.ins_runs = r.del_runs = 0;
@@ -593,15 +604,12 @@ void rec_summary(Rec &r, int read_len)
     }
     r.ref_span = r.m_bases + r.del_bases;
     r.summed = true;
-    // covered read interval, push_reg_res src/lamsa_aln.c:571-595
-    if (r.cigar.empty()) { r.reg_beg = 1; r.reg_end = read_len; return; }
-    const int32_t c0 = r.cigar.front(), c1 = r.cigar.back();
-    if (r.nstrand == 1) { r.reg_beg = (c0 & 0xf) == 4 ? (c0 >> 4) + 1 : 1; r.reg_end = (c1 & 0xf) == 4 ? read_len - (c1 >> 4) : read_len; }
-    else { r.reg_beg = (c1 & 0xf) == 4 ? (c1 >> 4) + 1 : 1; r.reg_end = (c0 & 0xf) == 4 ? read_len - (c0 >> 4) : read_len; }
+    cigar_read_interval(r.cigar, r.nstrand, read_len, r.reg_beg, r.reg_end);
 }
 
-void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm, bool summary)
+void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, int tags)
 {
+    const bool with_mm = (tags & LAMSA_HP_TAG_MISMATCHES) != 0, summary = (tags & LAMSA_HP_TAG_SUMMARY) != 0;
     // (R may hold an earlier read's result: its lines, records and CIGAR vectors are reused, not freed and allocated again)
     R.stage[2].clear();
     R.status = n_words > 0 ? s[0] : LAMSA_HP_ST_OVERFLOW;
@@ -625,27 +633,10 @@ void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bo
                 r.cigar.assign(s + i, s + i + cn); i += cn;
                 if (with_mm) { const int nm = s[i]; r.mm.assign(s + i + 1, s + i + 1 + nm); i += 1 + nm; }
                 else r.mm.clear();
-                // covered read interval, push_reg_res src/lamsa_aln.c:571-595
-                if (r.cigar.empty()) { r.reg_beg = 1; r.reg_end = read_len; continue; }
-                const int32_t c0 = r.cigar.front(), c1 = r.cigar.back();
-                if (r.nstrand == 1) { r.reg_beg = (c0 & 0xf) == 4 ? (c0 >> 4) + 1 : 1; r.reg_end = (c1 & 0xf) == 4 ? read_len - (c1 >> 4) : read_len; }
-                else { r.reg_beg = (c1 & 0xf) == 4 ? (c1 >> 4) + 1 : 1; r.reg_end = (c0 & 0xf) == 4 ? read_len - (c0 >> 4) : read_len; }
+                cigar_read_interval(r.cigar, r.nstrand, read_len, r.reg_beg, r.reg_end);
             }
         }
     }
-}
-
-// the mismatch lists of rounds 1 and 2 from the read and the .pac, for a library without lamsa_hp_set_result_tags
-static void host_mismatches(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix)
-{
-    std::vector<uint8_t> rc;
-    for (int st = 0; st < 2; ++st)
-        for (Line &ln : R.stage[st])
-            for (Rec &r : ln.rec) {
-                if (r.nstrand == 0 && rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
-                AuxCounts k;
-                if (!rec_aux(ix, r.nstrand ? bseq : rc.data(), read_len, r, k)) R.status |= LAMSA_HP_ST_REFEXIT;
-            }
 }
 
 void rec_left_align(Rec &r, const uint8_t *rd, int read_len, const Index &ix)
@@ -670,19 +661,6 @@ void rec_left_align(Rec &r, const uint8_t *rd, int read_len, const Index &ix)
         if (op == 0 || op == 1 || op == 4) q += k;
         if (op == 0 || op == 2) p += k;
     }
-}
-
-// rec_left_align on the records of rounds 1 and 2, each with the read on its own strand, for a library without lamsa_hp_set_result_tags
-// (the stage-4 records are shifted where they are made: rescue_finish)
-static void reads_left_align(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix)
-{
-    std::vector<uint8_t> rc;
-    for (int st = 0; st < 2; ++st)
-        for (Line &ln : R.stage[st])
-            for (Rec &r : ln.rec) {
-                if (r.nstrand == 0 && rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
-                rec_left_align(r, r.nstrand ? bseq : rc.data(), read_len, ix);
-            }
 }
 
 void rec_to_eqx(Rec &r)
@@ -711,6 +689,32 @@ void rec_to_eqx(Rec &r)
         }
     }
     r.cigar.swap(out);
+}
+
+bool rec_finish(Rec &r, const uint8_t *oriented_read, int read_len, const Index &ix, int what, AuxCounts *counts)
+{
+    if (what & FIN_LEFT_ALIGN) rec_left_align(r, oriented_read, read_len, ix);
+    if (what & FIN_AUX) { AuxCounts k; if (!rec_aux(ix, oriented_read, read_len, r, k)) return false; if (counts) *counts = k; }
+    if (what & FIN_EQX) rec_to_eqx(r);
+    if (what & FIN_SUMMARY) rec_summary(r, read_len);
+    return true;
+}
+
+const uint8_t *oriented_read(const uint8_t *bseq, int len, int nstrand, std::vector<uint8_t> &rc)
+{
+    if (nstrand == 1) return bseq;
+    if (rc.empty()) { rc.resize((size_t)len); for (int i = 0; i < len; ++i) rc[(size_t)i] = bseq[len - 1 - i] < 4 ? 3 - bseq[len - 1 - i] : 4; }
+    return rc.data();
+}
+
+void read_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, int what)
+{
+    if (!what || R.status != 0) return;
+    std::vector<uint8_t> rc;
+    for (int st = 0; st < 2; ++st)
+        for (Line &ln : R.stage[st])
+            for (Rec &r : ln.rec)
+                if (!rec_finish(r, oriented_read(bseq, read_len, r.nstrand, rc), read_len, ix, what)) R.status |= LAMSA_HP_ST_REFEXIT;
 }
 
 // a stable sort that allocates nothing for the handful of elements a read has (std::stable_sort asks for a buffer every time)
@@ -1256,18 +1260,16 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     const int G = (int)std::max<size_t>(1, hs.size());
     if (rc != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] no usable MI355X / HIP device (lamsa_hp_create: %d); this build has no CPU path\n", rc); return 2; }
     // --MD, --cs: every handle lists the mismatches of its records in the result stream; --eqx: it writes the CIGARs in =/X form;
-    // --left-align: it shifts the gaps before it counts.  Against a library without lamsa_hp_set_result_tags the host shifts the gaps
-    // (rec_left_align) and makes the lists (host_mismatches) and the =/X form (rec_to_eqx) itself, in that order.
-    const bool need_mm = opt.tag_md || opt.tag_cs;
-    // --paf: every handle ships a record's 15-word summary in place of its CIGAR (--left-align changes no word of it and is not passed on);
-    // without lamsa_hp_set_result_tags, under --paf-cg and for the stage-4 records the summaries are made from the CIGARs (rec_summary).
-    const bool paf_any = opt.paf || opt.paf_cg;
-    const int dev_tags = lamsa_hp_set_result_tags == nullptr ? 0 : opt.paf ? LAMSA_HP_TAG_SUMMARY :
+    // --left-align: it shifts the gaps before it counts.  --paf: every handle ships a record's 15-word summary in place of its CIGAR
+    // (--left-align changes no word of it and is not passed on).  What the output needs of every record is `fin_all` (rec_finish); what
+    // the device has done of it the host leaves out for rounds 1 and 2 (`what`) -- nothing against a library without
+    // lamsa_hp_set_result_tags, where the host does it all -- and the stage-4 records, made on the host, get all of it (rescue_finish).
+    const bool need_mm = opt.tag_md || opt.tag_cs, paf_any = opt.paf || opt.paf_cg, have_tags = lamsa_hp_set_result_tags != nullptr;
+    const int dev_tags = !have_tags ? 0 : opt.paf ? LAMSA_HP_TAG_SUMMARY :
                          (need_mm ? LAMSA_HP_TAG_MISMATCHES : 0) | (opt.tag_eqx ? LAMSA_HP_TAG_EQX : 0) | (opt.left_align ? LAMSA_HP_TAG_LEFT_ALIGN : 0);
-    const bool dev_sum = (dev_tags & LAMSA_HP_TAG_SUMMARY) != 0;
-    const bool dev_mm = (dev_tags & LAMSA_HP_TAG_MISMATCHES) != 0;
-    const bool host_mm = (need_mm || opt.tag_eqx) && lamsa_hp_set_result_tags == nullptr, host_eqx = opt.tag_eqx && !(dev_tags & LAMSA_HP_TAG_EQX);
-    const bool host_la = opt.left_align && !opt.paf && !(dev_tags & LAMSA_HP_TAG_LEFT_ALIGN);           // --left-align without the device item: rec_left_align, before the lists and the =/X form
+    const int fin_all = (opt.left_align && !opt.paf ? FIN_LEFT_ALIGN : 0) | (need_mm || opt.tag_eqx ? FIN_AUX : 0) | (opt.tag_eqx ? FIN_EQX : 0) | (paf_any ? FIN_SUMMARY : 0);
+    const int what = fin_all & ~((have_tags ? FIN_AUX : 0) | ((dev_tags & LAMSA_HP_TAG_LEFT_ALIGN) ? FIN_LEFT_ALIGN : 0) | ((dev_tags & LAMSA_HP_TAG_EQX) ? FIN_EQX : 0) |
+                                 ((dev_tags & LAMSA_HP_TAG_SUMMARY) ? FIN_SUMMARY : 0));
     for (lamsa_hp_handle *hh : hs) {
         if (!dev_tags) break;
         const int e = lamsa_hp_set_result_tags(hh, dev_tags);
@@ -1506,10 +1508,8 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             for (int r = r0; r < r1; ++r) {
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
-                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_mm, dev_sum);
-                if (host_la && R.status == 0) reads_left_align(R, codes + roff[r], L, ix);
-                if (host_mm && R.status == 0) host_mismatches(R, codes + roff[r], L, ix);
-                if (host_eqx && R.status == 0) for (int st = 0; st < 2; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) rec_to_eqx(x);
+                parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_tags);
+                read_finish(R, codes + roff[r], L, ix, what);
                 if (rescue && R.status == 0) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
             }
         });
@@ -1548,20 +1548,14 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             for (int r = t_first[(size_t)t]; r < t_last[(size_t)t]; ++r) {
                 ReadResult &R = RR[(size_t)r];
                 const int L = (int)B.reads[(size_t)r].seq.size();
-                if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) {
-                    rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp, opt.left_align != 0 && !opt.paf);      // stage-4 records: always shifted on the host, before their rec_aux (--paf: no word of a summary would change)
-                    if (opt.tag_eqx) for (Line &ln : R.stage[2]) for (Rec &x : ln.rec) rec_to_eqx(x);       // stage-4 records are made on the host, with their lists (rec_aux)
-                }
+                if (rescue && R.status == 0 && !plans[(size_t)r].lines.empty()) rescue_finish(R, codes + roff[r], L, ix, P, plans[(size_t)r], dp, fin_all);
                 if (R.status != 0) {
                     ++bad_of[(size_t)t];
                     fprintf(stderr, "[lamsa_aln] read %s: %s; reported unmapped\n", B.reads[(size_t)r].name.c_str(), (R.status & LAMSA_HP_ST_UNSUPPORTED) ? "more than 32767 seeds, or a seed hit with |len_dif| > 127: beyond what the device keeps" : (R.status & LAMSA_HP_ST_REFEXIT) ? "input on which the reference aligner exits" : "device work buffer overflow");
                     for (int st = 0; st < 3; ++st) R.stage[st].clear();
                 }
                 rank_results(R, L, P);
-                if (paf_any) {
-                    for (int st = 0; st < 3; ++st) for (Line &ln : R.stage[st]) for (Rec &x : ln.rec) if (!x.summed) rec_summary(x, L);
-                    write_paf(o, R, B.reads[(size_t)r], ix, opt);
-                }
+                if (paf_any) write_paf(o, R, B.reads[(size_t)r], ix, opt);
                 else write_sam(o, R, B.reads[(size_t)r], ix, opt);
             }
         });

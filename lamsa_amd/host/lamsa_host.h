@@ -72,9 +72,11 @@ struct XaRef { int st, li, ri; };
 struct Line { int line_score = 0, tol_score = 0, tol_NM = 0, merg_x = 0, merg_y = 0; uint8_t mapQ = 0; std::vector<Rec> rec; std::vector<XaRef> xa; };   // line_aln_res
 struct ReadResult { int status = 0; std::vector<Line> stage[3]; };   // aln_res[3]: first round, remain round, BWT rescue (empty)
 
-// with_mm: the stream carries the records' mismatch lists (lamsa_hp_set_result_tags(h, LAMSA_HP_TAG_MISMATCHES))
-// summary: the records are the 15 words of LAMSA_HP_TAG_SUMMARY (no CIGAR, no list)
-void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, bool with_mm = false, bool summary = false);
+// tags: what lamsa_hp_set_result_tags was given.  LAMSA_HP_TAG_MISMATCHES: the stream carries the records' mismatch lists;
+// LAMSA_HP_TAG_SUMMARY: the records are the 15 words of the item (no CIGAR, no list)
+void parse_stream(const int32_t *s, int n_words, int read_len, ReadResult &R, int tags = 0);
+// a record's covered read interval (1-based, forward strand) from its CIGAR, strand and the read's length
+void cigar_read_interval(const std::vector<int32_t> &cigar, int nstrand, int read_len, int &beg, int &end);
 // the eight summary words of include/lamsa_hp.h (LAMSA_HP_TAG_SUMMARY) from the record's CIGAR, ops 0, 7 and 8 alike: reg_beg, reg_end and the
 // six fields behind `summed`.  For --paf-cg, for a library without lamsa_hp_set_result_tags, and for the records stage 4 makes on the host
 void rec_summary(Rec &r, int read_len);

@@ -413,7 +413,7 @@ bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts
     return ok && read_i == read_len && ref_i == ref_len;
 }
 
-void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, bool left_align)
+void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, int what)
 {
     std::vector<Line> &out = R.stage[2];
     out.clear();
@@ -442,24 +442,15 @@ void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index
             push1(r.cigar, ((L.reg_len - L.right.read_pos + L.right_eta) << 4) | 4);
         }
         push1(r.cigar, ((L.is_rev ? L.extra_beg - 1 : read_len - L.extra_end) << 4) | 4);
-        // lamsa_res_aux, src/frag_check.c:793-848, on this one record
-        const uint8_t *rd = bseq;
-        if (L.is_rev) {
-            if (rc.empty()) { rc.resize((size_t)read_len); for (int i = 0; i < read_len; ++i) rc[(size_t)i] = bseq[read_len - 1 - i] < 4 ? 3 - bseq[read_len - 1 - i] : 4; }
-            rd = rc.data();
-        }
-        if (left_align) rec_left_align(r, rd, read_len, ix);           // --left-align: before anything is counted or listed, as on the device
+        // lamsa_res_aux, src/frag_check.c:793-848, on this one record (and whatever else `what` asks for, in rec_finish's order)
         AuxCounts k;
-        if (!rec_aux(ix, rd, read_len, r, k)) { R.status |= LAMSA_HP_ST_REFEXIT; return; }      // the reference exits with "Unmatched length"
+        if (!rec_finish(r, oriented_read(bseq, read_len, r.nstrand, rc), read_len, ix, what | FIN_AUX, &k)) { R.status |= LAMSA_HP_ST_REFEXIT; return; }      // the reference exits with "Unmatched length"
         r.NM = k.n_mm + k.n_ie + k.n_de;
         r.score = k.n_m * P.match - k.n_mm * P.mis - k.n_io * P.ins_gapo - k.n_ie * P.ins_gape - k.n_do * P.del_gapo - k.n_de * P.del_gape;
         int cur_res_n = 0;
         if (r.score < 0) cur_res_n = -1; else { la.tol_score += r.score; la.tol_NM += r.NM; }
         if (cur_res_n < 0) la.tol_score = -1; else la.tol_score -= cur_res_n * P.split_pen;
-        // covered interval of the record, push_reg_res :571
-        const int32_t c0 = r.cigar.front(), c1 = r.cigar.back();
-        if (r.nstrand == 1) { r.reg_beg = (c0 & 0xf) == 4 ? (c0 >> 4) + 1 : 1; r.reg_end = (c1 & 0xf) == 4 ? read_len - (c1 >> 4) : read_len; }
-        else { r.reg_beg = (c1 & 0xf) == 4 ? (c1 >> 4) + 1 : 1; r.reg_end = (c0 & 0xf) == 4 ? read_len - (c0 >> 4) : read_len; }
+        cigar_read_interval(r.cigar, r.nstrand, read_len, r.reg_beg, r.reg_end);
         bool accept = true;
         if (P.read_type > 0) {                                  // solid_readInCigar(...) > 0.5 * reg_len, :376
             int solid = 0;

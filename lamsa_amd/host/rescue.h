@@ -59,7 +59,17 @@ struct DpResults { const int32_t *score, *qle, *tle; const int64_t *cig_off; con
 struct AuxCounts { int n_mm = 0, n_m = 0, n_io = 0, n_ie = 0, n_do = 0, n_de = 0; };
 bool rec_aux(const Index &ix, const uint8_t *rd, int read_len, Rec &r, AuxCounts &k);
 
-// finish: DP results -> R.stage[2]; left_align: the gaps of every record are left-aligned (rec_left_align) before rec_aux walks it
-void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, bool left_align = false);
+// What the host does to a record after the device (or stage 4) has made it, always in the order the device applies the items of
+// lamsa_hp_set_result_tags in: gaps left-aligned (rec_left_align), mismatches listed and counted (rec_aux), =/X form (rec_to_eqx), summary.
+enum { FIN_LEFT_ALIGN = 1, FIN_AUX = 2, FIN_EQX = 4, FIN_SUMMARY = 8 };
+// the steps of `what` on one record; counts: what rec_aux counted.  false: rec_aux failed (the caller flags LAMSA_HP_ST_REFEXIT), no later step was made
+bool rec_finish(Rec &r, const uint8_t *oriented_read, int read_len, const Index &ix, int what, AuxCounts *counts = nullptr);
+// the read on a record's strand: bseq for '+', else its reverse complement, made in `rc` the first time a '-' record of the read asks
+const uint8_t *oriented_read(const uint8_t *bseq, int read_len, int nstrand, std::vector<uint8_t> &rc);
+// rec_finish on the records of rounds 1 and 2 of a read that has status 0
+void read_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, int what);
+
+// finish: DP results -> R.stage[2], every record through rec_finish(what | FIN_AUX): its score and NM come from that walk
+void rescue_finish(ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, const DpResults &dp, int what = 0);
 
 }  // namespace lamsa

@@ -4,7 +4,7 @@
 // the flags -- and one record through out_line, so that the 15-lane store is seen next to guard words.
 #include "emu_eqx.cpp"
 
-// 1 if lamsa_hp_set_result_tags accepts `flags` (result_tags_valid, hp_align.h: the product's routine calls the same function)
+// 1 if lamsa_hp_set_result_tags accepts `flags` (result_tags_valid, hp_out.h: the product's routine calls the same function)
 extern "C" int emu_result_tags_valid(int flags) { return result_tags_valid(flags) ? 1 : 0; }
 
 // emu_align_batch_tags behind that check: LAMSA_HP_EINVAL and nothing written for flags the product refuses

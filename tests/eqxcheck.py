@@ -8,15 +8,11 @@ import re
 
 import numpy as np
 
+from streamwalk import rebuild, revcomp_codes
 from tagcheck import CIG_RE, NT4, ref_codes
 
 OPS = "MIDNSHP=X"
 C_M, C_I, C_D, C_S, C_H, C_EQ, C_X = 0, 1, 2, 4, 5, 7, 8
-
-
-def revcomp_codes(read):
-    read = np.asarray(read, np.uint8)
-    return np.where(read[::-1] < 4, 3 - read[::-1], 4).astype(np.uint8)
 
 
 def _pieces(q, t):
@@ -78,23 +74,13 @@ def cs_of(words, read_codes, pac, k0):
 # ---- the result stream (include/lamsa_hp.h), without mismatch lists
 def stream_to_eqx(s, read, pac, seq_off):
     """A read's flag-off stream with every record's cigar_n and CIGAR words replaced by the =/X form."""
-    s = list(s)
-    if len(s) < 3 or s[0] != 0:
-        return s
     read = np.asarray(read, np.uint8)
     rc = revcomp_codes(read)
-    out, i = s[:3], 3
-    for _ in range(s[1] + s[2]):
-        out += s[i:i + 4]
-        n_res = s[i + 3]; i += 4
-        for _ in range(n_res):
-            off = (s[i] & 0xffffffff) | (s[i + 1] << 32)
-            chr_, strand, cn = s[i + 2], s[i + 3], s[i + 6]
-            e = to_eqx(s[i + 7:i + 7 + cn], read if strand == 1 else rc, pac, int(seq_off[chr_ - 1]) + off - 1)
-            out += s[i:i + 6] + [len(e)] + e
-            i += 7 + cn
-    assert i == len(s), "stream not consumed"
-    return out
+
+    def eqx(r):
+        e = to_eqx(r.cig, read if r.nstrand == 1 else rc, pac, r.k0(seq_off))
+        return r.hdr[:6] + [len(e)] + e
+    return rebuild(s, eqx)
 
 
 # ---- SAM text

@@ -17,7 +17,8 @@ import re
 
 import numpy as np
 
-from eqxcheck import _SA_RE, _XA_RE, collapse, revcomp_codes, text_of, words_of
+from eqxcheck import _SA_RE, _XA_RE, collapse, text_of, words_of
+from streamwalk import rebuild, revcomp_codes
 from tagcheck import NT4, ref_codes
 
 C_M, C_I, C_D, C_S, C_H = 0, 1, 2, 4, 5
@@ -83,23 +84,9 @@ def check_consequences(before, after):
 # ---- the result stream (include/lamsa_hp.h), without mismatch lists
 def stream_left_aligned(s, read, pac, seq_off, stats=None):
     """A read's flag-off stream with the CIGAR words of every record replaced by the left-aligned ones; no other word changes."""
-    s = list(s)
-    if len(s) < 3 or s[0] != 0:
-        return s
     read = np.asarray(read, np.uint8)
     rc = revcomp_codes(read)
-    out, i = s[:3], 3
-    for _ in range(s[1] + s[2]):
-        out += s[i:i + 4]
-        n_res = s[i + 3]; i += 4
-        for _ in range(n_res):
-            off = (s[i] & 0xffffffff) | (s[i + 1] << 32)
-            chr_, strand, cn = s[i + 2], s[i + 3], s[i + 6]
-            c = left_align(s[i + 7:i + 7 + cn], read if strand == 1 else rc, pac, int(seq_off[chr_ - 1]) + off - 1, stats)
-            out += s[i:i + 7] + c
-            i += 7 + cn
-    assert i == len(s), "stream not consumed"
-    return out
+    return rebuild(s, lambda r: r.hdr + left_align(r.cig, read if r.nstrand == 1 else rc, pac, r.k0(seq_off), stats))
 
 
 # ---- SAM text

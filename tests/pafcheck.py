@@ -6,6 +6,8 @@ n_res; per record offset_lo, offset_hi, chr, nstrand, score, NM, cigar_n and cig
 record is these seven words and q_beg, q_end, ref_span, m_bases, ins_bases, del_bases, ins_runs, del_runs."""
 import re
 
+from streamwalk import walk
+
 M, I, D, S, H, EQ, X = 0, 1, 2, 4, 5, 7, 8
 
 
@@ -38,31 +40,24 @@ def summary_words(cigar, nstrand, read_len, stats=None):
 def stream_summaries(words, read_len, para=None, stats=None):
     """The flag-off stream of one read -> the stream LAMSA_HP_TAG_SUMMARY must give.  Asserts the two identities on every record:
     n_mm = NM - ins_bases - del_bases >= 0, and (with para, an object with the scoring fields) the score formula."""
-    out = list(words[:3])
-    if len(words) < 3 or words[0] != 0:
-        assert len(words) <= 3
-        return out
-    i = 3
-    for _ in range(words[1] + words[2]):
-        out += words[i:i + 4]
-        n_res = words[i + 3]
-        i += 4
-        if stats is not None:
-            stats["multi_rec"] += n_res > 1
-        for _ in range(n_res):
-            hdr = words[i:i + 7]
-            cn = hdr[6]
-            cig = words[i + 7:i + 7 + cn]
-            i += 7 + cn
-            s = summary_words(cig, hdr[3], read_len, stats)
-            q_beg, q_end, ref_span, m, ins, dele, io, do = s
-            n_mm = hdr[5] - ins - dele
-            assert n_mm >= 0, (hdr, s)
-            assert 1 <= q_beg <= q_end <= read_len, (hdr, s)
-            if para is not None:
-                assert hdr[4] == (m - n_mm) * para.match - n_mm * para.mis - io * para.ins_gapo - ins * para.ins_gape - do * para.del_gapo - dele * para.del_gape, (hdr, s)
-            out += hdr + s
-    assert i == len(words)
+    out = []
+    for kind, x in walk(words):
+        if kind == "head":
+            assert len(x) <= 3
+        elif kind == "line" and stats is not None:
+            stats["multi_rec"] += x[3] > 1
+        if kind != "rec":
+            out += x
+            continue
+        hdr = x.hdr
+        s = summary_words(x.cig, hdr[3], read_len, stats)
+        q_beg, q_end, ref_span, m, ins, dele, io, do = s
+        n_mm = hdr[5] - ins - dele
+        assert n_mm >= 0, (hdr, s)
+        assert 1 <= q_beg <= q_end <= read_len, (hdr, s)
+        if para is not None:
+            assert hdr[4] == (m - n_mm) * para.match - n_mm * para.mis - io * para.ins_gapo - ins * para.ins_gape - do * para.del_gapo - dele * para.del_gape, (hdr, s)
+        out += hdr + s
     return out
 
 

@@ -5,6 +5,8 @@ import re
 
 import numpy as np
 
+from streamwalk import rebuild, records, revcomp_codes
+
 MD_RE = re.compile(r"^[0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*$")
 NT4 = np.full(256, 4, np.uint8)
 for _i, _c in enumerate("ACGT"):
@@ -111,49 +113,32 @@ def check_sam(text, pac, contig_off):
 # ---- the result stream (include/lamsa_hp.h: lamsa_hp_result)
 def split_events(s):
     """A read's stream with mismatch lists -> (the stream without them, [per record: list of event words])."""
-    s = list(s)
-    if len(s) < 3 or s[0] != 0:
-        return s, []
-    out, ev, i = s[:3], [], 3
-    for _ in range(s[1] + s[2]):
-        out += s[i:i + 4]
-        n_res = s[i + 3]; i += 4
-        for _ in range(n_res):
-            cn = s[i + 6]
-            out += s[i:i + 7 + cn]; i += 7 + cn
-            nm = s[i]
-            ev.append(s[i + 1:i + 1 + nm]); i += 1 + nm
-    assert i == len(s), "stream not consumed"
-    return out, ev
+    ev = []
+
+    def strip(r):
+        ev.append(r.mm)
+        return r.hdr + r.cig
+    return rebuild(s, strip, lists=True), ev
 
 
 def stream_events(s, read, pac, seq_off):
     """The mismatch lists recomputed from a stream without them: per record (offset, chr, strand, CIGAR) against the read's
     codes (`read`, forward strand) and the .pac (`seq_off`: .pac offset of each contig)."""
     read = np.asarray(read, np.uint8)
-    rc = np.where(read[::-1] < 4, 3 - read[::-1], 4).astype(np.uint8)
-    ev, i = [], 3
-    if len(s) < 3 or s[0] != 0:
-        return ev
-    for _ in range(s[1] + s[2]):
-        n_res = s[i + 3]; i += 4
-        for _ in range(n_res):
-            off = (s[i] & 0xffffffff) | (s[i + 1] << 32)
-            chr_, strand, cn = s[i + 2], s[i + 3], s[i + 6]
-            cig = s[i + 7:i + 7 + cn]; i += 7 + cn
-            q = read if strand == 1 else rc
-            w = np.asarray(cig, np.int64)
-            op, ln = w & 0xf, w >> 4
-            qs = np.concatenate([[0], np.cumsum(np.where((op == 0) | (op == 1) | (op == 4), ln, 0))])[:-1]
-            rs = np.concatenate([[0], np.cumsum(np.where((op == 0) | (op == 2), ln, 0))])[:-1]
-            m = op == 0
-            n = int(ln[m].sum())
-            start = np.repeat(np.cumsum(ln[m]) - ln[m], ln[m])                # index of each aligned base within the M runs
-            j = np.arange(n) - start
-            qi, ri = np.repeat(qs[m], ln[m]) + j, np.repeat(rs[m], ln[m]) + j
-            k0 = int(seq_off[chr_ - 1]) + off - 1
-            t = ref_codes(pac, k0, int(rs[-1] + (ln[-1] if op[-1] in (0, 2) else 0)) if len(op) else 0)
-            d = np.nonzero(q[qi] != t[ri])[0]
-            e = (ri[d] << 2 | t[ri[d]].astype(np.int64)).tolist()
-            ev.append(e)
+    rc = revcomp_codes(read)
+    ev = []
+    for r in records(s):
+        q = read if r.nstrand == 1 else rc
+        w = np.asarray(r.cig, np.int64)
+        op, ln = w & 0xf, w >> 4
+        qs = np.concatenate([[0], np.cumsum(np.where((op == 0) | (op == 1) | (op == 4), ln, 0))])[:-1]
+        rs = np.concatenate([[0], np.cumsum(np.where((op == 0) | (op == 2), ln, 0))])[:-1]
+        m = op == 0
+        n = int(ln[m].sum())
+        start = np.repeat(np.cumsum(ln[m]) - ln[m], ln[m])                # index of each aligned base within the M runs
+        j = np.arange(n) - start
+        qi, ri = np.repeat(qs[m], ln[m]) + j, np.repeat(rs[m], ln[m]) + j
+        t = ref_codes(pac, r.k0(seq_off), int(rs[-1] + (ln[-1] if op[-1] in (0, 2) else 0)) if len(op) else 0)
+        d = np.nonzero(q[qi] != t[ri])[0]
+        ev.append((ri[d] << 2 | t[ri[d]].astype(np.int64)).tolist())
     return ev
