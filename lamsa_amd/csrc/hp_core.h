@@ -88,7 +88,13 @@ struct Ctx {
 //  the walk / in cut_branch, 56 end nodes on the image whose chain of more than 64 nodes is marked by the chase through `from`,
 //  58 / 59 get_max_son on the image: a son that ties the best on max_score at another seed distance / at the same one (max_NM decides), 60 a son skipped for its edge
 //  class once a match-class son is held, 61 largest clusters refused by the packing checks, 62 cut_branch on the image with three or more sons, 63 reads with a resident cluster whose first pass
-//  takes every hit (all_min); largest value: 57 resident cluster
+//  takes every hit (all_min); largest value: 57 resident cluster;
+//  SV junctions (tests/sv_cases.py), through HP_STATX_ADD / HP_STATX_MAX (below) only: split_sv (hp_fill.h) 64 DEL through ksw_bi_extend, 65 DEL through the split mapper, 66 overlapped
+//  INS, 67 / 68 DUP through the mapper with ref_offset = -dis / 0 (window cut at the contig's end), 69 DUP through ksw_bi_extend; the split mapper (hp_split.h) 70 windows
+//  with a unique k-mer (MIN route), 71 nodes promoted by hash_min_extend, 72 hmini_main_line calls, 73 windows without an anchor; its anchor walk: 74 / 75 / 76 the left blank
+//  by ksw_global / ksw_bi_extend / indel_cigar, 77 / 78 / 79 the right blank likewise, 80 / 81 between anchors by ksw_global / ksw_bi_extend, 82 overlap on the reference,
+//  83 pure indel, 84 indels of split_pen bases or more, 85 / 86 no anchor: ksw_global / ksw_bi_extend; 89 read k-mers dropped for more than HP_HASH_MAX_HITS matches,
+//  90 / 91 hnode_dis on an insertion of split_len / 2 bases or more with ref_offset > 0 / == 0; largest values: 87 n_codes, 88 matches of a k-mer that was kept
 #ifndef HP_DPLOG
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { } while (0)      // tests' CPU build: one record per DP call (tools/dp_shapes.py)
 #endif
@@ -102,6 +108,17 @@ struct Ctx {
 #endif
 #ifndef HP_STAT_MAX
 #define HP_STAT_MAX(i, v) ((void)0)
+#endif
+// Slots from 64 on (the SV junctions) go through HP_STATX_ADD / HP_STATX_MAX: they count only in a CPU build that says how many slots its array has
+// (HP_STAT_SLOTS, tests/emu/emu_api.cpp).  A CPU build whose array ends at slot 63 and the device build see an empty expression, so no slot is
+// ever written behind an array that was not made for it.
+#ifdef HP_STAT_SLOTS
+static_assert(HP_STAT_SLOTS >= 92, "the array of the path counters ends before the last slot the device sources use");
+#define HP_STATX_ADD(i, n) HP_STAT_ADD(i, n)
+#define HP_STATX_MAX(i, v) HP_STAT_MAX(i, v)
+#else
+#define HP_STATX_ADD(i, n) ((void)0)
+#define HP_STATX_MAX(i, v) ((void)0)
 #endif
 
 // returns nullptr (and flags overflow) when the slab is exhausted; callers must cope

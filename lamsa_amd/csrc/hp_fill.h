@@ -558,8 +558,8 @@ HP_NOINL bool split_sv(ReadCtx &r, const JGeo &g, Rec &res)
         ok = tb && cig_alloc(cx, sc, s_qlen + s_tlen + 64) && ref_fetch(r, at1_chr, at1_off + P->seed_len + at1_ld - 1, &tl, tb);
         if (ok) {
             s_tlen = tl;
-            if (s_qlen < hash_len) ksw_bi_extend(cx, s_qlen, seq_fwd(qp), s_tlen, seq_fwd(tb), gh0, gh0, sc);
-            else split_indel_map(cx, sc, qp, s_qlen, tb, s_tlen, 0);
+            if (s_qlen < hash_len) { HP_STATX_ADD(64, 1); ksw_bi_extend(cx, s_qlen, seq_fwd(qp), s_tlen, seq_fwd(tb), gh0, gh0, sc); }
+            else { HP_STATX_ADD(65, 1); split_indel_map(cx, sc, qp, s_qlen, tb, s_tlen, 0); }
         }
     } else {                                                      // INS, :490-546
         s_tlen = s_qlen + dis;
@@ -575,6 +575,7 @@ HP_NOINL bool split_sv(ReadCtx &r, const JGeo &g, Rec &res)
                 ok = ref_fetch(r, at2_chr, at2_off - _s_tlen - 1, &_s_tlen, tb2);
             }
             if (ok) {
+                HP_STATX_ADD(66, 1);
                 const Seq rq = seq_rev(qp, s_qlen), rt = seq_rev(tb2, _s_tlen);
                 ksw_extend(cx, s_qlen, rq, _s_tlen, rt, P->band_w, gh0, &rqe, &rte, &rcg);
                 cig_invert(rcg.c, rcg.n);
@@ -589,8 +590,8 @@ HP_NOINL bool split_sv(ReadCtx &r, const JGeo &g, Rec &res)
                 s_tlen = tl;
                 const int off_dis = (s_tlen != s_qlen - dis + 2 * hash_len) ? 0 : -dis;
                 s_tlen = s_qlen + dis;
-                if (s_tlen < hash_len) ksw_bi_extend(cx, s_qlen, seq_fwd(qp), s_tlen, seq_fwd(tb + hash_len - dis), gh0, gh0, sc);
-                else split_indel_map(cx, sc, qp, s_qlen, tb + hash_len - dis, s_tlen, off_dis);
+                if (s_tlen < hash_len) { HP_STATX_ADD(69, 1); ksw_bi_extend(cx, s_qlen, seq_fwd(qp), s_tlen, seq_fwd(tb + hash_len - dis), gh0, gh0, sc); }
+                else { HP_STATX_ADD(off_dis ? 67 : 68, 1); split_indel_map(cx, sc, qp, s_qlen, tb + hash_len - dis, s_tlen, off_dis); }
             }
         }
     }

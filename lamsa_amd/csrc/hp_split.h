@@ -44,10 +44,12 @@ HP_FN int hnode_dis(const HCtx &c, int a_i, int a_offset, int b_i, int b_offset)
     if (dis >= -(gap - hash_len)) return F_INSERT;
     if (dis <= -(c.P->split_len / 2)) {
         if (ref_offset > 0) {
+            HP_STATX_ADD(90, 1);
             if (b_i > a_i) return (read_len - ref_len + b_offset >= -(a_i + hash_len - 1) && read_len - a_offset >= b_i) ? F_INSERT : F_UNCONNECT;
             HP_STAT(11);
             return (read_len - ref_len + a_offset >= -(b_i + hash_len - 1) && read_len - b_offset >= a_i) ? F_INSERT : F_UNCONNECT;
         }
+        HP_STATX_ADD(91, 1);
         if (b_i > a_i) return (b_offset >= -(a_i - 1) && ref_len - a_offset >= b_i) ? F_INSERT : F_UNCONNECT;
         HP_STAT(12);
         return (a_offset >= -(b_i - 1) && ref_len - b_offset >= a_i) ? F_INSERT : F_UNCONNECT;
@@ -115,13 +117,14 @@ HP_FN int hmain_line(Ctx &cx, HCtx &c, int hash_seed_n, int32_t *line)
         else hnode_init_from(c, i, head, MULTI_FLAG);
     }
     if (min_exist) {
+        HP_STATX_ADD(70, 1);
         for (int i = 1; i <= hash_seed_n; ++i) {                     // hash_min_extend, :312-338
             if (c.len_a[i] <= 1) continue;
             for (int a = c.nstart[i], ae = c.nstart[i] + c.len_a[i]; a < ae; ++a) {
                 if (c.h_dp[a] < 0) continue;
                 for (int j = 0; j < hash_seed_n + 2; ++j) {
                     if (c.len_a[j] != 1) continue;
-                    if (c.h_offset[a] == c.h_offset[c.nstart[j]]) { c.h_dp[a] = MIN_FLAG; break; }
+                    if (c.h_offset[a] == c.h_offset[c.nstart[j]]) { c.h_dp[a] = MIN_FLAG; HP_STATX_ADD(71, 1); break; }
                 }
             }
         }
@@ -136,6 +139,7 @@ HP_FN int hmain_line(Ctx &cx, HCtx &c, int hash_seed_n, int32_t *line)
         node_i = 0;
         for (int guard = 0; guard < hash_seed_n + 4; ++guard) {
             if (c.h_match[right] != F_MATCH && hslot_of(c, left) < c.h_slot[right] - 1) {
+                HP_STATX_ADD(72, 1);
                 const int mini_len = hmini_main_line(c, left, right, _line);
                 for (int i = mini_len - 1; i >= 0 && node_i < hash_seed_n; --i) line[node_i++] = _line[i];
             }
@@ -169,8 +173,8 @@ HP_FN int indel_cigar(Ctx &cx, int ref_left, int read_left, int ref_right, int r
     const int dlen = ref_left - ref_right + 1, ilen = read_left - read_right + 1;
     if (dlen < 0 && ilen < 0) { cx.status |= ST_REFEXIT; *clen = 0; return 0; }
     const int len = ilen - dlen;
-    if (len > 0) { *clen = 1; cg[0] = (len << 4) + C_D; if (len >= split_len) *split_flag |= 2; }
-    else if (len < 0) { *clen = 1; cg[0] = ((0 - len) << 4) + C_I; if (-len >= split_len) *split_flag |= 2; }
+    if (len > 0) { *clen = 1; cg[0] = (len << 4) + C_D; if (len >= split_len) { HP_STATX_ADD(84, 1); *split_flag |= 2; } }
+    else if (len < 0) { *clen = 1; cg[0] = ((0 - len) << 4) + C_I; if (-len >= split_len) { HP_STATX_ADD(84, 1); *split_flag |= 2; } }
     else *clen = 0;
     return dlen > ilen ? dlen : ilen;
 }
@@ -188,6 +192,7 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
     const size_t mark = arena_mark(cx.tmp);
     const int n_codes = ref_len - hash_len + 1 > 0 ? ref_len - hash_len + 1 : 0;
     const int hash_seed_n = (read_len - hash_len) / hash_step + 1;
+    HP_STATX_MAX(87, n_codes);
     uint32_t *rcode = (uint32_t *)arena_alloc(cx, sizeof(uint32_t) * (size_t)(n_codes + 1));
     int32_t *nstart = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)(hash_seed_n + 3));
     int32_t *len_a = (int32_t *)arena_alloc(cx, sizeof(int32_t) * (size_t)(hash_seed_n + 3));
@@ -209,6 +214,7 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
             cnt += __builtin_popcountll(wv::ballot(eq));
         }
         len_a[s] = cnt > HP_HASH_MAX_HITS ? 0 : cnt;
+        HP_STATX_MAX(88, len_a[s]); HP_STATX_ADD(89, cnt > HP_HASH_MAX_HITS ? 1 : 0);
         nn += len_a[s];
     }
     len_a[hash_seed_n + 1] = 1; ++nn;
@@ -256,10 +262,11 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
         int _refi = HN_RI(0) + HN_OF(0), _readi = HN_RI(0);
         _q_len = _readi + tail_in; _t_len = _refi + tail_in;
         if (_readi != 0 && _refi != 0) {                                  // 1. left blank, :700-715
-            if (_t_len < P->split_len && _q_len < P->split_len) HP_GLOBAL(_q_len, read_seq, _t_len, ref_seq);
-            else res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq), _t_len, seq_fwd(ref_seq), gh0, gh0, tmp);
+            if (_t_len < P->split_len && _q_len < P->split_len) { HP_STATX_ADD(74, 1); HP_GLOBAL(_q_len, read_seq, _t_len, ref_seq); }
+            else { HP_STATX_ADD(75, 1); res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq), _t_len, seq_fwd(ref_seq), gh0, gh0, tmp); }
             cig_pushv(cx, out, tmp.c, tmp.n);
         } else {
+            HP_STATX_ADD(76, 1);
             indel_cigar(cx, -1, -1, _refi, _readi, g, &_clen, split_len, &res);
             if (_clen) cig_pushw(cx, out, g[0]);
             cig_push1(cx, out, (tail_in << 4) | C_M);
@@ -275,12 +282,13 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
             if (l_readi + 1 < r_readi && l_refi + 1 < r_refi) {
                 _q_len = r_readi - (l_readi + 1) + head_in + tail_in;
                 _t_len = _q_len + r_offset - l_offset;
-                if (_q_len < P->split_len && _t_len < P->split_len) HP_GLOBAL(_q_len, read_seq + l_readi + 1 - head_in, _t_len, ref_seq + l_refi + 1 - head_in);
-                else res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq + l_readi + 1 - head_in), _t_len, seq_fwd(ref_seq + l_refi + 1 - head_in), gh0, gh0, tmp);
+                if (_q_len < P->split_len && _t_len < P->split_len) { HP_STATX_ADD(80, 1); HP_GLOBAL(_q_len, read_seq + l_readi + 1 - head_in, _t_len, ref_seq + l_refi + 1 - head_in); }
+                else { HP_STATX_ADD(81, 1); res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq + l_readi + 1 - head_in), _t_len, seq_fwd(ref_seq + l_refi + 1 - head_in), gh0, gh0, tmp); }
                 cig_pushv(cx, out, tmp.c, tmp.n);
                 overlap = 0;
             } else if (l_refi >= r_refi) {                                // overlap on the reference, :746-775
                 int lqe, lte, rqe, rte;
+                HP_STATX_ADD(82, 1);
                 _q_len = r_readi - (l_readi + 1) + head_in;
                 _t_len = _q_len + (ref_offset > 0 ? hash_len : 0);
                 ksw_extend(cx, _q_len, seq_fwd(read_seq + l_readi + 1 - head_in), _t_len, seq_fwd(ref_seq + l_refi + 1 - head_in), P->band_w, gh0, &lqe, &lte, &tmp);
@@ -299,6 +307,7 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
                 cig_pushv(cx, out, tmp.c, tmp.n);
                 overlap = 0;
             } else {
+                HP_STATX_ADD(83, 1);
                 cig_push1(cx, out, (head_in << 4) | C_M);
                 overlap = indel_cigar(cx, l_refi, l_readi, r_refi, r_readi, g, &_clen, split_len, &res);
                 if (_clen) cig_pushw(cx, out, g[0]);
@@ -310,18 +319,20 @@ HP_NOINL int split_indel_map(Ctx &cx, CigV &out, const uint8_t *read_seq, int re
         _refi = HN_RI(m_len - 1) + HN_OF(m_len - 1) + hash_len - 1;
         _q_len = read_len - (_readi + 1) + head_in; _t_len = ref_len - (_refi + 1) + head_in;
         if (_readi + 1 < read_len && _refi + 1 < ref_len) {
-            if (_q_len < P->split_len && _t_len < P->split_len) HP_GLOBAL(_q_len, read_seq + _readi + 1 - head_in, _t_len, ref_seq + _refi + 1 - head_in);
-            else res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq + _readi + 1 - head_in), _t_len, seq_fwd(ref_seq + _refi + 1 - head_in), gh0, gh0, tmp);
+            if (_q_len < P->split_len && _t_len < P->split_len) { HP_STATX_ADD(77, 1); HP_GLOBAL(_q_len, read_seq + _readi + 1 - head_in, _t_len, ref_seq + _refi + 1 - head_in); }
+            else { HP_STATX_ADD(78, 1); res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq + _readi + 1 - head_in), _t_len, seq_fwd(ref_seq + _refi + 1 - head_in), gh0, gh0, tmp); }
             cig_pushv(cx, out, tmp.c, tmp.n);
         } else {
+            HP_STATX_ADD(79, 1);
             cig_push1(cx, out, (head_in << 4) | C_M);
             indel_cigar(cx, _refi, _readi, ref_len, read_len, g, &_clen, split_len, &res);
             if (_clen) cig_pushw(cx, out, g[0]);
         }
     } else {                                                              // no anchors, :807-819
         _t_len = ref_len; _q_len = read_len;
-        if (_t_len < P->split_len && _q_len < P->split_len) HP_GLOBAL(_q_len, read_seq, _t_len, ref_seq);
-        else res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq), _t_len, seq_fwd(ref_seq), gh0, gh0, tmp);
+        HP_STATX_ADD(73, 1);
+        if (_t_len < P->split_len && _q_len < P->split_len) { HP_STATX_ADD(85, 1); HP_GLOBAL(_q_len, read_seq, _t_len, ref_seq); }
+        else { HP_STATX_ADD(86, 1); res |= ksw_bi_extend(cx, _q_len, seq_fwd(read_seq), _t_len, seq_fwd(ref_seq), gh0, gh0, tmp); }
         cig_pushv(cx, out, tmp.c, tmp.n);
     }
 #undef HN_RI

@@ -20,7 +20,8 @@ int g_emu_pk = 1;                      // tests: 0 = extensions of 63 .. 254 que
 std::vector<long long> g_emu_dplog;    // one record per DP call of the fill: kind (0 extension, 1 global), query, target, band, cells
 int g_emu_dplog_on = 0;
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { if (g_emu_dplog_on) { g_emu_dplog.push_back(kind); g_emu_dplog.push_back(qlen); g_emu_dplog.push_back(tlen); g_emu_dplog.push_back(w); g_emu_dplog.push_back(cells); } } while (0)
-long long g_emu_stat[64];              // path counters (HP_STAT / HP_STAT_MAX slots of the device sources, listed in hp_core.h)
+#define HP_STAT_SLOTS 128             // slots of g_emu_stat; the device sources count the slots from 64 on only when this is said (hp_core.h)
+long long g_emu_stat[HP_STAT_SLOTS];              // path counters (HP_STAT / HP_STAT_MAX slots of the device sources, listed in hp_core.h)
 #define HP_STAT(i) (++g_emu_stat[i])
 #define HP_STAT_ADD(i, n) (g_emu_stat[i] += (n))
 #define HP_STAT_MAX(i, v) do { if ((long long)(v) > g_emu_stat[i]) g_emu_stat[i] = (long long)(v); } while (0)
@@ -128,7 +129,7 @@ extern "C" void emu_set_wave_jobs(int on) { g_emu_wave_jobs = on; }
 extern "C" void emu_set_wj_small(int bytes) { g_emu_wj_small = bytes; }
 extern "C" void emu_set_pk(int on) { g_emu_pk = on; }
 extern "C" void emu_set_frag_block_min(int n) { g_emu_frag_block_min = n > 0 ? n : 3; }
-extern "C" long long emu_stat(int i) { return g_emu_stat[i & 63]; }
+extern "C" long long emu_stat(int i) { return g_emu_stat[i & (HP_STAT_SLOTS - 1)]; }
 extern "C" void emu_dplog_on(int on) { g_emu_dplog_on = on; g_emu_dplog.clear(); }
 extern "C" long long emu_dplog(long long *buf, long long cap) { long long n = (long long)g_emu_dplog.size(); for (long long i = 0; i < n && i < cap; ++i) buf[i] = g_emu_dplog[i]; return n; }
 extern "C" void emu_stat_reset() { memset(g_emu_stat, 0, sizeof g_emu_stat); }

@@ -446,7 +446,7 @@ def end_extension_from_oracle(jobs, lp, head, w, h0):
 
 
 CHAIN_LDS_WORDS = (2432, 3392, 5120)          # LDS words per wave of the three shapes of the chaining kernels (hp_align_api.hip: g_chain_shapes)
-N_STATS = 64
+N_STATS = 128
 
 
 def emu_guard_hits(E=None):

@@ -290,7 +290,8 @@ def _split_cases(rng, hash_len):
 def test_kmer_split_mapper_three_ways(preset):
     """split_indel_map (src/split_mapping.c:829: k-mer index of the window, bucket matching, hash DP, indel CIGAR) on crafted gaps: the
     device code under the lane emulation == the oracle == the REFERENCE itself (oracle/_ref, when built).  The gaps without a unique
-    k-mer run the MULTI pass of the hash DP (hp_split.h hmain_line, src/split_mapping.c:570-581), which no read of the corpus reaches."""
+    k-mer run the MULTI pass of the hash DP (hp_split.h hmain_line, src/split_mapping.c:570-581), which no read of the corpus reaches; the
+    hand-made reads of tests/sv_cases.py reach it through the whole path (tests/test_sv_cpu.py, and tests/test_sv_gpu.py on the device)."""
     from lamsa_amd.hp import HpPara
     import ctypes
     lp = reflib.lo_para(preset)
