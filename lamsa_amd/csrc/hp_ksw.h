@@ -928,23 +928,42 @@ HP_NOINL ExtRes ksw_extend_regn(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
 
 // ksw_extend_core for LONG queries -- the end extensions of a line, up to the whole read (frag_head_bound_fix / frag_tail_bound_fix,
 // src/frag_check.c:576-707) -- with the row's live WINDOW in registers, int16 pairs, 2 * NS consecutive columns per lane.
-// A row of the extension only touches the columns [beg, end], at most 2w + 2 of them, and the window only moves right: column j of the
-// reference's eh[] array lives in slot j mod (128 * NS) -- lane (j / (2 NS)) mod 64, register (j mod 2 NS) / 2, half j & 1 -- so a lane holds
-// 2 NS neighbouring columns (NS registers of pairs), then the 2 NS columns 128 NS further on, and so on; the slots of columns the band has
-// left behind are given to the columns ahead of it eight lanes at a time, with the value the reference's first-row initialisation left
-// there (:692-694), i.e. what it reads from its full-length array when the band reaches a cell it never wrote.
+// A row of the extension only touches the columns [beg, end], at most 2w + 2 of them, and the band only moves right.  The window is WN = 128 NS
+// columns of the reference's eh[] array in plain column order: lane l holds the LC = 2 NS columns base + LC l .. base + LC l + LC - 1 (NS registers
+// of pairs), `base` a wave-uniform multiple of LC that starts at 0.  One discipline, two cases:
+//   * the window holds the whole query (qlen + 3 <= WN, FIXED: most calls, the junctions): base stays 0 and column j stays in slot j;
+//   * it does not (the long end extensions): when the band's right edge nears the window's (end + 3 > base + WN, tested before the row is computed)
+//     the window is RE-BASED: every state register moves down by s = (beg - base) / LC lanes (wv::gather), the s lanes freed at the top load the
+//     columns behind the old window with the value the reference's first-row initialisation left there (:692-694), i.e. what it reads from
+//     its full-length array when the band reaches a cell it never wrote, and base += s LC.  Columns below beg are never read again (beg never
+//     decreases), so nothing is lost.  s >= 9: end <= beg + 2w + 1 and pkb_sets_q's first clause, 2w + 3 + 9 LC <= WN, turn end + 3 > base + WN into
+//     beg - base > 9 LC - 1.  s <= 63: the row before passed the test, so beg <= max(its end, its beg + 1) < base + WN.  Afterwards base > beg - LC, hence
+//     end + 3 <= beg + 2w + 4 <= base + LC - 1 + 2w + 4 <= base + WN: the test holds again.  A full band re-bases every (WN - 2w - 3) / LC lanes' worth
+//     of rows -- about 50 rows for ont2d (NS 2, w 100), about 100 for the other presets -- and between two re-bases every row is the FIXED body.
+// What the rows rely on: lane numbers are column order, so ONE exclusive prefix maximum over the lanes carries F along the row (lanes outside the
+// band contribute the identity), the band shrink reads first / last set lane of a ballot as they are, and H(i, end - 1) sits in lane
+// (end - 1 - base) / LC.  The test above leaves end <= base + WN - 3, so lane 63's last column, base + WN - 1, lies outside [beg, end): it holds -1 in
+// hcur and the one-lane rotation (wv::ror1) feeds lane 0 that -1, "not computed", for its first column -- which is <= beg and takes no H from the left.
 // What that buys over the LDS tiles (ksw_extend_lds: 64 columns per pass, ~90 instructions and eight LDS operations each, four passes
 // for a band of 201): everything a row does across lanes is done ONCE per row whatever NS -- the F scan (a lane scans its own columns,
-// then one exclusive prefix maximum over the lanes' totals, in two halves where the window may wrap round the wave), the row maximum
-// (one reduction of (H << 16 | column) keys: "last column among equals" is the larger key, :743-744), the one-column shift of H (inside
-// a lane but for one wave rotation), the first and last non-zero cell (:775-778: a ballot over the lanes, then two lanes' bit patterns).
-// Same recurrences, tie rules, band and z-drop logic as ksw_extend_reg; scores are bounded (pkb_extend_ok), the scan's keys use
-// columns relative to the row's first one (the sliding window) or to column 0 (the fixed one, below).  The direction matrix is a nibble per
-// cell in the wave's slab, a row = 64 * NS bytes indexed by the slot, with the band limits of every row beside it.
-// Two variants of the one body (round 9): most calls are junctions whose whole query fits the window (qlen + 3 <= 128 NS: 70 % of the
-// routine's wave cycles on 10-kbp ONT reads, profiles/r04_dp_routines.txt) and never use the circular window's machinery; FIXED compiles it out.
-// The row loop in the gfx950 ISA, all paths, VALU / scalar instructions: NS = 1 197 / 164 before, fixed 116 / 134, sliding 191 / 196; NS = 2
-// 339 / 255 before, fixed 199 / 139, sliding 329 / 250 (profiles/r09_extband_ab.txt -- static counts; that file says what has been timed).
+// then the prefix maximum over the lanes' totals), the row maximum (one reduction of (H << 16 | column) keys: "last column among
+// equals" is the larger key, :743-744), the one-column shift of H (inside a lane but for one wave rotation), the first and last non-zero cell
+// (:775-778: a ballot over the lanes, then two lanes' bit patterns).
+// Same recurrences, tie rules, band and z-drop logic as ksw_extend_reg; scores are bounded (pkb_extend_ok).  With one and two sets the scan's keys
+// use columns relative to `base`: (j - base) * e_ins is a constant of the LANE that a re-base does not change, set once per job (below 8 000 by
+// pkb_extend_ok's (128 NS + 2) * ext; F(i, beg) = 0 is (beg - base) * e_ins in that frame).  With four sets holding it costs four registers
+// through the loop and spills, so there the keys stay relative to beg and the term is worked out again after the scan.
+// The direction matrix is a nibble per cell in the wave's slab (HBM), a row = 64 * NS bytes; a cell stays at slot column mod WN whatever the
+// base, so a lane's byte offset in the row is ((base / LC + l) & 63) * NS, kept in a register and renewed by a re-base; dp_backtrack, the band
+// limits of every row beside the matrix, and the slab sizes know nothing of the window.
+// History and numbers: round 9 split off the FIXED case from a circular window (column j in slot j mod WN, refilled eight lanes at a time, a second
+// scan over the lanes that had wrapped round, every lane index and ballot rotated by the window's first lane); the re-based window replaced the
+// circular one.  Row loop in the gfx950 ISA, all paths (the re-base block included), VALU, circular -> re-based -> with the two items below: NS = 1 fixed
+// 116 -> 116 -> 107, sliding 191 -> 187 -> 172; NS = 2 fixed 199 -> 199 -> 190, sliding 329 -> 320 -> 305; NS = 4 fixed 380 -> 380 -> 375, sliding 617 -> 637 -> 632
+// (its re-base block is larger than the refill was; its rows' main block 278 -> 275 -> 274: the keys stay relative to beg there).  The main block of a
+// sliding row: NS = 1 91 -> 77, NS = 2 152 -> 136, three more than the fixed one.  The two items: the row maximum is lane 63 of a six-step scan (-5 VALU a
+// row), and with one and two sets the band limits of 64 rows sit in lane i & 63 of two registers (pkb_putlane2) and are stored once per block of target
+// rows (-4 .. -5; with four sets the two registers spill).  Measured, each alone and together: profiles/rebase_window_ab.txt.
 // sets for a query of qlen columns under band w: the window holds the band + 2 + the eight lanes being refilled + one lane of slack -- or the
 // whole query, and then never moves
 HP_INL int pkb_sets_q(int qlen, int w)
@@ -977,10 +996,23 @@ HP_INL int pkb_key_hi(int h, int j)
     return (int)(((unsigned)h & 0xffff0000u) | ((unsigned)j >> 16));
 #endif
 }
-// FIXED: the window holds the whole query (qlen + 3 <= 128 * NS), so column j stays in slot j from the first row to the last -- the lanes are in
-// column order as they are, and everything the circular window needs per row is compiled out: the refill test, the second scan over the lanes
-// that wrapped round, the rotation of lanes and ballots by the window's first lane, and the scan keys' column term, which is taken relative
-// to column 0 (j * e_ins < 8 000 by pkb_extend_ok, as (j - beg) * e_ins was) and is then a constant of the lane for the whole job.
+// lane `dst` (0 .. 63) of a takes the wave-uniform value va, that of b takes vb: wv::setlane twice, in one vector instruction each (v_writelane_b32)
+// on the device.  The instruction may name one SGPR only, so the lane select goes through m0, which is saved and put back (the compiler is not
+// told about m0); scalar moves write it, so the hazard "VALU writes an SGPR -> lane select of v_writelane" cannot arise.  The CPU build and the
+// host pass take wv::setlane.
+HP_INL void pkb_putlane2(wv::Lane<int> &a, wv::Lane<int> &b, int dst, int va, int vb)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int keep;
+    asm("s_mov_b32 %2, m0\n\ts_mov_b32 m0, %5\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0\n\ts_mov_b32 m0, %2"
+        : "+v"(a.v), "+v"(b.v), "=&s"(keep) : "s"(va), "s"(vb), "s"(dst));
+#else
+    wv::setlane(a, dst, va); wv::setlane(b, dst, vb);
+#endif
+}
+// FIXED: the window holds the whole query (qlen + 3 <= 128 * NS) and never re-bases: the test, the re-base block, `base` (0) and the register with
+// a lane's place in a row of the direction matrix are compiled out.  The parameter stays because the junction rows must not pay for a register
+// they do not need (their static counts, 116 and 199 VALU, are the same as before the re-based window).
 template <int NS, bool FIXED>
 HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w, int h0, CigV *out)
 {
@@ -996,7 +1028,9 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
     const int n_col = qlen < 2 * w + 1 ? qlen : 2 * w + 1;
     // the scan keys' column term: j * e_ins, a constant of the lane, where the window is fixed -- but not with four sets, where holding four more
     // registers through the row loop spills; there it stays (j - beg) * e_ins and is worked out again after the scan instead of held across it
-    constexpr bool KEY0 = FIXED && NS < 4, KEEP_JRE = NS < 4;
+    constexpr bool KEY0 = NS < 4;
+    // the band limits of 64 rows in two registers, stored once per block -- not with four sets, where two more registers through the row loop spill
+    constexpr bool LIM_LANES = NS < 4;
     constexpr int LC = 2 * NS, WN = 128 * NS, zs = 64 * NS;              // columns per lane, slots of the window, bytes of a row of the direction matrix
     const size_t mark = arena_mark(cx.tmp);
     uint8_t *z = (uint8_t *)arena_alloc(cx, (size_t)zs * tlen + 16);
@@ -1027,16 +1061,16 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
             Hs[r_][l] = pk::pack(hv_[0], hv_[1]); Es[r_][l] = 0; qoh[r_][l] = oh_; qN[r_][l] = nn_; \
         } \
         JB[l] = pk::pack(jb_, (jb_) + 1); } while (0)
-    wv::Lane<int> Hs[NS], Es[NS], qoh[NS], qN[NS], hcur[NS], M[NS], INB[NS], JRE[NS], pre[NS], JB, tl;
-    WAVE_FOR(l) { tl[l] = 4; HP_PKB_LOAD(LC * l); }
+    wv::Lane<int> Hs[NS], Es[NS], qoh[NS], qN[NS], hcur[NS], M[NS], INB[NS], JRE[NS], pre[NS], JB, tl, zoff, RB, RE;
+    WAVE_FOR(l) { tl[l] = 4; HP_PKB_LOAD(LC * l); zoff[l] = NS * l; RB[l] = 0; RE[l] = 0; }
     if constexpr (FIXED) HP_STAT(16);
     if constexpr (KEY0) {
         WAVE_FOR(l) {
 #pragma unroll
-            for (int r = 0; r < NS; ++r) JRE[r][l] = pk::mul(pk::add(JB[l], pk::rep(2 * r)), EI);
+            for (int r = 0; r < NS; ++r) JRE[r][l] = pk::mul(pk::add(JB[l], pk::rep(2 * r)), EI);       // (base is 0 here: the column in the window's frame)
         }
     }
-    int top = WN; (void)top;                                               // columns [0, top) have been given their slots
+    int base = 0; (void)base;                                              // the window's first column: lane l holds base + LC * l .. base + LC * l + LC - 1
     int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1;
     int beg = 0, end = qlen;
     bool stop_rows = false;
@@ -1046,13 +1080,15 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
         { WAVE_FOR(l) { const int ii = ib + l; tl[l] = ii < tlen ? gt[(long)ii * ts] : 4; } }
         const int ti_first = wv::bcast(tl, 0);
         const int ie = ib + 64 < tlen ? ib + 64 : tlen;
+        int n_lim = 0; (void)n_lim;                                              // rows of this block whose band limits RB / RE hold
         for (int i = ib; i < ie; ++i) {
             const int ti = i == ib ? ti_first : wv::bcast(tl, i & 63);
             if (beg < i - w) beg = i - w;                                  // :718-720
             if (end > i + w + 1) end = i + w + 1;
             if (end > qlen) end = qlen;
             cells_ += end > beg ? end - beg : 0;
-            { WAVE_FOR(l) { if (l < 2) growb[2 * i + l] = l ? end : beg; } }
+            if constexpr (LIM_LANES) { pkb_putlane2(RB, RE, i & 63, beg, end); n_lim = i - ib + 1; }      // the row's band limits: lane i & 63, stored with the block's
+            else { WAVE_FOR(l) { if (l < 2) growb[2 * i + l] = l ? end : beg; } }
             int h1_init;
             if (beg == 0) { h1_init = h0 - (o_del + e_del * (i + 1)); if (h1_init < 0) h1_init = 0; }
             else h1_init = 0;
@@ -1061,17 +1097,30 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 if (beg == qlen) { max_ie = gscore > h1_init ? max_ie : i; gscore = gscore > h1_init ? gscore : h1_init; }       // :759-762 (the loop variable stands at beg)
                 stop_rows = true; break;
             }
-            if (!FIXED && end + 3 > top) {                                 // the band's right edge (next row's at most two further) nears the loaded columns: eight more lanes
-                const int lr = (top / LC) & 63;
-                WAVE_FOR(l) { const int d = (l - lr) & 63; if (d < 8) { const int jb = top + d * LC; HP_PKB_LOAD(jb); } }
-                top += 8 * LC;
+            if constexpr (!FIXED) {
+                if (end + 3 > base + WN) {                                 // the band's right edge (next row's at most two further) nears the window's: re-base
+                    // s whole lanes below the band are dropped: end <= beg + 2w + 1 and 2w + 3 + 9 LC <= WN give beg - base >= 9 LC, so s >= 9; the last row passed
+                    // this test, so its end, and with it beg, lies below base + WN - 2 and s <= 63; the new base lies above beg - LC, so end + 3 <= base + WN again
+                    const int s = (beg - base) / LC;
+                    HP_STATX_ADD(92, 1); HP_STATX_MAX(93, s); HP_STATX_MAX(94, 64 - s); HP_STATX_ADD(95, i == ib ? 1 : 0); HP_STATX_ADD(96, (i & 63) == 63 ? 1 : 0);
+                    base += s * LC;
+                    wv::Lane<int> from;
+                    WAVE_FOR(l) from[l] = (l + s) & 63;
+#pragma unroll
+                    for (int r = 0; r < NS; ++r) { Hs[r] = wv::gather(Hs[r], from); Es[r] = wv::gather(Es[r], from); qoh[r] = wv::gather(qoh[r], from); qN[r] = wv::gather(qN[r], from); }
+                    WAVE_FOR(l) {
+                        const int jb = base + LC * l;
+                        if (l >= 64 - s) HP_PKB_LOAD(jb);                  // the freed lanes: the columns behind the old window, as the first row left them
+                        JB[l] = pk::pack(jb, jb + 1);
+                        zoff[l] = ((base / LC + l) & 63) * NS;             // a cell's place in its row of the direction matrix stays column mod WN
+                    }
+                }
             }
             const int tsh = ti & 3, tN = ti > 3 ? -1 : 0;                   // a target N scores -1 against everything
             const int BEG = pk::rep(beg), END = pk::rep(end), H1 = pk::rep(h1_init);
-            const int l0 = FIXED ? 0 : (beg / LC) & 63;                    // the lane of the window's first column: lanes l0 .. 63, then 0 .. l0 - 1, hold ascending columns
-            const int F0 = KEY0 ? pk::rep(beg * e_ins) : 0;                // F(i,beg) = 0 carried along the row, in the keys' frame
-            // ---- the lane's own columns: M, the scan keys max(M - oe_ins, 0) + (j - beg) * e_ins (KEY0: j * e_ins) and their running maximum
-            wv::Lane<int> ka, kb;
+            const int F0 = KEY0 ? pk::rep((beg - base) * e_ins) : 0;       // F(i,beg) = 0 carried along the row, in the keys' frame
+            // ---- the lane's own columns: M, the scan keys max(M - oe_ins, 0) + (j - beg) * e_ins (KEY0: (j - base) * e_ins) and their running maximum
+            wv::Lane<int> ka;
             WAVE_FOR(l) {
                 int run = HP_PK_IDENT;
 #pragma unroll
@@ -1088,26 +1137,21 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                     const int klo = pk::lo(k), khi = pk::hi(k);
                     const int p0 = run; run = run > klo ? run : klo;
                     const int p1 = run; run = run > khi ? run : khi;
-                    M[r][l] = m; INB[r][l] = in; if constexpr (!KEY0 && KEEP_JRE) JRE[r][l] = jre; pre[r][l] = pk::pack(p0, p1);
+                    M[r][l] = m; INB[r][l] = in; pre[r][l] = pk::pack(p0, p1);
                 }
-                if constexpr (FIXED) { ka[l] = run; kb[l] = HP_PK_IDENT; }
-                else { ka[l] = l >= l0 ? run : HP_PK_IDENT; kb[l] = l < l0 ? run : HP_PK_IDENT; }
+                ka[l] = run;
             }
-            // F along the row: the exclusive prefix maximum over the lanes before this one in column order -- one scan when the window never
-            // moves, two when it may have wrapped round the wave.  (Round 4 tried the single scan behind a per-row test inside the one routine:
-            // no gain, the rest of the circular window's bookkeeping stayed.  As a routine of its own: profiles/r09_extband_ab.txt.)
-            int topA = HP_PK_IDENT;
-            if constexpr (FIXED) wv::scan_max_excl(ka, HP_PK_IDENT);
-            else { topA = wv::scan_max_excl_top(ka, HP_PK_IDENT); wv::scan_max_excl(kb, HP_PK_IDENT); }
+            // F along the row: the exclusive prefix maximum over the lanes before this one -- the lanes are in column order, and lanes outside the band
+            // contribute the identity
+            wv::scan_max_excl(ka, HP_PK_IDENT);
             wv::Lane<int> best;
             WAVE_FOR(l) {
-                const int pl = FIXED ? ka[l] : (l >= l0 ? ka[l] : (topA > kb[l] ? topA : kb[l]));
-                const int PP = pk::rep(pl);
+                const int PP = pk::rep(ka[l]);
                 int zw = 0, bk = -1;
 #pragma unroll
                 for (int r = 0; r < NS; ++r) {
                     const int jp = pk::add(JB[l], pk::rep(2 * r));
-                    const int jre = KEEP_JRE ? JRE[r][l] : pk::mul(pk::sub(jp, BEG), EI);
+                    const int jre = KEY0 ? JRE[r][l] : pk::mul(pk::sub(jp, BEG), EI);
                     const int in = INB[r][l], m = M[r][l];
                     const int pr = pk::max(pre[r][l], PP);
                     int f = pk::max(pk::add(pk::sub(pr, jre), EI), pk::sub(F0, jre));                       // F(i,beg) = 0 carried along the row
@@ -1133,12 +1177,15 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                     bk = bk > k0 ? bk : k0; bk = bk > k1 ? bk : k1;
                 }
                 best[l] = bk;
-                if constexpr (NS == 1) gz[(long)i * zs + l] = (uint8_t)zw;
-                else if constexpr (NS == 2) *(HP_G uint16_t *)(gz + (long)i * zs + 2 * l) = (uint16_t)zw;
-                else *(HP_G uint32_t *)(gz + (long)i * zs + 4 * l) = (uint32_t)zw;
+                const int zo = FIXED ? NS * l : zoff[l];
+                if constexpr (NS == 1) gz[(long)i * zs + zo] = (uint8_t)zw;
+                else if constexpr (NS == 2) *(HP_G uint16_t *)(gz + (long)i * zs + zo) = (uint16_t)zw;
+                else *(HP_G uint32_t *)(gz + (long)i * zs + zo) = (uint32_t)zw;
             }
             int mrow = 0, mj = -1;
-            { const int b = wv::reduce_max(best); if (b >= 0) { mrow = b >> 16; mj = b & 0xffff; } }
+            // (the maximum is lane 63 of an inclusive scan: six DPP steps and one readlane, against four steps, four readlanes and three scalar maxima of
+            // wv::reduce_max; the scan's own result is not used)
+            { const int b = wv::scan_max_excl_top(best, -1); if (b >= 0) { mrow = b >> 16; mj = b & 0xffff; } }
             // eh[j+1].h = H(i,j): the row one column up -- inside the lane, and the lane's first column from the lane below's last
             wv::Lane<int> rot = hcur[NS - 1], LB;
             wv::ror1(rot);
@@ -1161,7 +1208,7 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 LB[l] = bits;
             }
             if (end == qlen) {                                             // :759-762, with H(i, end - 1) -- only these rows need it
-                const int le = FIXED ? (end - 1) / LC : ((end - 1) / LC) & 63, sl = (end - 1) % LC;
+                const int le = (end - 1 - base) / LC, sl = (end - 1) % LC;
                 int v = 0;
 #pragma unroll
                 for (int r = 0; r < NS; ++r) if ((sl >> 1) == r) v = wv::bcast(hcur[r], le);
@@ -1180,11 +1227,9 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 const unsigned long long any = wv::ballot(LB);
                 int nb = end, jl = end - 1;
                 if (any) {
-                    const unsigned long long rt = l0 ? ((any >> l0) | (any << (64 - l0))) : any;          // bit d: the lane d lanes after l0
-                    const int df = __builtin_ctzll(rt), dl = 63 - __builtin_clzll(rt);
-                    const int bf = wv::bcast(LB, FIXED ? df : (l0 + df) & 63), bl = wv::bcast(LB, FIXED ? dl : (l0 + dl) & 63);
-                    const int bb = FIXED ? 0 : beg / LC;                   // (FIXED: a lane's number is its place in column order)
-                    const int jf = (bb + df) * LC + __builtin_ctz((unsigned)bf), jx = (bb + dl) * LC + (31 - __builtin_clz((unsigned)bl));
+                    const int df = __builtin_ctzll(any), dl = 63 - __builtin_clzll(any);                  // a lane's number is its place in column order
+                    const int bf = wv::bcast(LB, df), bl = wv::bcast(LB, dl);
+                    const int jf = base + df * LC + __builtin_ctz((unsigned)bf), jx = base + dl * LC + (31 - __builtin_clz((unsigned)bl));
                     if (jf < end) nb = jf;
                     jl = jx;                                               // (index `end` alone: nb = end, jl = end)
                 }
@@ -1192,6 +1237,8 @@ HP_NOINL ExtRes ksw_extend_band(Ctx &cx, int qlen, Seq q, int tlen, Seq t, int w
                 end = jl + 2 < qlen ? jl + 2 : qlen;
             }
         }
+        // the band limits of the block's rows, one store (every way out of the row loop passes here)
+        if constexpr (LIM_LANES) WAVE_FOR(l) { if (l < n_lim) { hp_v2i be; be.x = RB[l]; be.y = RE[l]; *(HP_G hp_v2i *)(growb + 2 * (ib + l)) = be; } }
     }
 #undef HP_PKB_LOAD
 #undef HP_PKB_EH0

@@ -7,8 +7,11 @@
 // merge_cigar (:251), which joins their results, is sequential -- so the listing launch (phase_filllist, hp_phase.h) writes them as job
 // records with the geometry the fill would compute, and this launch runs them one per wavefront, costliest first: a launch that is all
 // instruction issue (VALU port 100 % busy, profiles/r04_ont10k_pmc.json; 87 lane-slots per cell update against ~22 for the recurrence -- round 9 cut the row loop of the
-// extensions whose window never moves by ~40 % of its instructions, profiles/r09_extband_ab.txt, not yet timed) before a fill launch that is all memory latency (wait 85 %), instead of one kernel that is both; the
-// direction matrix of the two-columns-per-lane routines lies in the wave's LDS where it fits (a junction of up to 80 rows).  The fill finds the
+// extensions whose window never moves by ~40 % of its instructions, profiles/r09_extband_ab.txt; the re-based window took the circular window's
+// bookkeeping out of the long end extensions' rows, profiles/rebase_window_ab.txt) before a fill launch that is all memory latency (wait 85 %), instead of one kernel that is both; the
+// direction matrix of the register-set and LDS-row routines and of the packed global alignment (ksw_extend_reg / _regn / _lds, ksw_global_reg / _lds / _pk)
+// lies in the wave's LDS where it fits (a junction of up to 80 rows); that of the
+// window routine (ksw_extend_band) always lies in the wave's slab in HBM, 64 / 128 / 256 bytes a row.  The fill finds the
 // CIGARs in the job arena (FLines::jt / gt / ht) and goes on with merge_cigar; a job that was not listed, or whose buffers did not suffice, is
 // run by the fill as before.
 // The routines are those of hp_ksw.h: same recurrences, tie rules, band and z-drop logic, whatever launch calls them.
