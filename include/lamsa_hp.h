@@ -93,7 +93,12 @@ const char *lamsa_hp_last_error(const lamsa_hp_handle *h);
  *           ksw_extend_c (:809) with (w, h0); unless the query was consumed the rest of it is appended as a soft clip, and the head's
  *           CIGAR is turned round (frag_head_bound_fix / frag_tail_bound_fix, src/frag_check.c:640-648, :699-703); score / qle / tle
  *           are the extension's.
- *   One class (0-2, 4-6, 8-11) per call.
+ *   kind 12, 13: a job as the read path's lane launches run it, listed into their queues and run stage by stage (queries of 1 .. 64 and
+ *           targets of up to 160 bases without N; the handle's penalties must fit the lane routines): 12 = a junction's
+ *           ksw_bi_extend(100, 100), 13 = a seed gap's ksw_global2(band_w); w and h0 are not read.  status 0 = the CIGAR was left for the
+ *           fill to pick up (1: the fill would run the job itself), qle = DP cells charged to the job, tle = 1 when the job went through
+ *           a hard queue (the second stage), score 0.
+ *   One class (0-2, 4-6, 8-11, 12-13) per call.
  * Sequences are 1 byte/base codes 0..4; job i uses query seq[q_off[i] .. q_off[i]+qlen[i])
  * and target seq[t_off[i] .. t_off[i]+tlen[i]).
  * ---------------------------------------------------------------------------------- */

@@ -130,23 +130,35 @@ __global__ __launch_bounds__(64, HP_LIST_WAVES_PER_SIMD) void k_filllist(const P
         phase_filllist(a, round, u, blockIdx.x, (HP_L int32_t *)lds, r);
     }
 }
-// the lane-per-job DP over the round's queues (hp_lanedp.h): 64 jobs per wave, rows of HP_LJ_QSMALL cells per lane in LDS
+// the lane-per-job DP over the round's queues (hp_lanedp.h): 64 jobs per wave, rows of HP_LJ_QSMALL cells per lane in LDS.  One kernel per stage of
+// phase_filldp (hp_phase.h): LJ_STAGE1 over the queues the lister filled, LJ_STAGE2 over the hard queues the first stage filled, each with the DP
+// routines of its stage only; LJ_ONE (diagnostics) is the whole of it in one launch.
+template <int MODE>
 __global__ __launch_bounds__(64, 2) void k_filldp_small(const PhaseArgs *ap, int round)
 {
     __shared__ int32_t lds[HP_LJ_LDS_WORDS(HP_LJ_QSMALL)];
     const PhaseArgs &a = *ap;
+    constexpr int b0 = MODE == LJ_STAGE2 ? LJ_NORD : 0, b1 = MODE == LJ_STAGE2 ? LJ_NBUCKET : LJ_NORD, head = MODE == LJ_STAGE2 ? 9 : 6;
     int n = 0;
-    for (int b = 0; b < LJ_NBUCKET; ++b) n += (lj_queue_n(a, round, b) + 63) >> 6;
+    for (int b = b0; b < b1; ++b) n += (lj_queue_n(a, round, b) + 63) >> 6;
     n = wv::uni(n);
     for (;;) {
         int g = 0;
-        if (wv::leader()) g = atomicAdd(&a.ctl->q_head[6], 1);
+        if (wv::leader()) g = atomicAdd(&a.ctl->q_head[head], 1);
         g = wv::uni(g);
         if (g >= n) break;
-        int b = 0;
-        for (; b < LJ_NBUCKET - 1; ++b) { const int gb = (lj_queue_n(a, round, b) + 63) >> 6; if (g < gb) break; g -= gb; }
-        phase_filldp(a, round, b, g * 64, blockIdx.x, (HP_L int32_t *)lds, HP_LJ_QSMALL);
+        int b = b0;
+        for (; b < b1 - 1; ++b) { const int gb = (lj_queue_n(a, round, b) + 63) >> 6; if (g < gb) break; g -= gb; }
+        if (MODE == LJ_STAGE2 && b < LJ_NORD + LJ_NCLS) phase_filldp_run<LJ_STAGE2G>(a, round, b, g * 64, blockIdx.x, (HP_L int32_t *)lds, HP_LJ_QSMALL);      // (jobs that only need ksw_global2)
+        else phase_filldp_run<MODE>(a, round, b, g * 64, blockIdx.x, (HP_L int32_t *)lds, HP_LJ_QSMALL);
     }
+}
+// both stages of a round on one stream, the second right behind the first
+static void launch_filldp(bool stages, int w_dp, hipStream_t s, const PhaseArgs *da, int round)
+{
+    if (!stages) { hipLaunchKernelGGL(k_filldp_small<LJ_ONE>, dim3(w_dp), dim3(64), 0, s, da, round); return; }
+    hipLaunchKernelGGL(k_filldp_small<LJ_STAGE1>, dim3(w_dp), dim3(64), 0, s, da, round);
+    hipLaunchKernelGGL(k_filldp_small<LJ_STAGE2>, dim3(w_dp), dim3(64), 0, s, da, round);
 }
 // the wave-per-job DP (hp_wavejob.h): the junctions beyond a lane job, the end extensions of every line; costliest class first.
 __global__ __launch_bounds__(64, HP_WJ_WAVES_PER_SIMD) void k_filldp_wave(const PhaseArgs *ap, int round)
@@ -236,6 +248,7 @@ static const bool g_trace = getenv("LAMSA_HP_TRACE") != nullptr;      // phase t
 static const bool g_noshare = getenv("LAMSA_HP_FULL_GRIDS") != nullptr;   // diagnostics: full-size grids also when two batches are in flight (slab_plan)
 static const bool g_nowave = getenv("LAMSA_HP_NO_WAVE_JOBS") != nullptr; // diagnostics: skip the wave-per-job DP launch (the fill then runs the junctions beyond a lane job and the end extensions itself)
 static const bool g_nolane = getenv("LAMSA_HP_NO_LANE_DP") != nullptr;  // diagnostics: skip the lane-per-job DP launches (the fill then runs every DP itself, one job per wave)
+static const bool g_lane_stages = !(getenv("LAMSA_HP_LANE_STAGES") && atoi(getenv("LAMSA_HP_LANE_STAGES")) == 0);   // diagnostics: LAMSA_HP_LANE_STAGES=0 runs the lane DP in one stage (one launch a round, no hard queues)
 static const bool g_mono = getenv("LAMSA_HP_ONE_KERNEL") != nullptr;  // diagnostics: the main pass through k_align_batch (the retry pass's kernel) instead of the phased launches
 
 struct HostBuf {                  // page-locked host memory, mapped into the device's address space
@@ -287,6 +300,9 @@ struct Slot {                     // one batch on the device: its inputs, the ou
                                   // that the waves of the next batch fill the SIMDs the tail of the previous one leaves idle
     bool valid = false;           // a batch is resident
     bool phased = false;          // the launch in flight on this slot's resources is the phased main pass
+#ifdef HP_LJ_STATS
+    const PhaseCtl *ctl_dev = nullptr;   // diagnostic build: that pass's counters on the device
+#endif
     int32_t n_reads = 0; int64_t n_bases = 0, n_cig = 0, n_hits = 0;
     BatchIn in; const int32_t *d_order = nullptr;
     std::vector<int32_t> order, h_len, h_H; std::vector<uint8_t> h_skip;      // h_skip: reads the batch check found beyond the device's field widths
@@ -598,7 +614,7 @@ static SlabPlan slab_plan(lamsa_hp_handle *h, int max_L, int max_H, bool shared 
     int pc = 0, pf = 0, pd = 0, pw = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, g_chain_shapes[shape].k1, 64, 0) != hipSuccess || pc < 1) pc = 4 * g_chain_shapes[shape].waves_per_simd;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pf, k_fill, 64, 0) != hipSuccess || pf < 1) pf = 4;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pd, k_filldp_small, 64, 0) != hipSuccess || pd < 1) pd = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pd, g_lane_stages ? k_filldp_small<LJ_STAGE2> : k_filldp_small<LJ_ONE>, 64, 0) != hipSuccess || pd < 1) pd = 4;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, k_filldp_wave, 64, 0) != hipSuccess || pw < 1) pw = 4;
     if (shared && !g_noshare) { pc = std::min(pc, 8); pf = std::min(pf, 16); pw = std::min(pw, 16); }
     // diagnostic: LAMSA_HP_FILL_PER_CU / LAMSA_HP_CHAIN_PER_CU / LAMSA_HP_WJ_PER_CU set the grids' waves per CU
@@ -656,6 +672,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
     if (Ln.args_host.ensure(sizeof a)) { h->err = "hipHostMalloc(args)"; return LAMSA_HP_ENOMEM; }
     memcpy(Ln.args_host.p, &a, sizeof a);                   // the slot's launch resources are not reused before this launch has been collected
     HIPCHK(h, hipMemcpyAsync(d + o_args, Ln.args_host.p, sizeof a, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    if (!g_lane_stages) HIPCHK(h, hipMemsetAsync(&((PhaseCtl *)(d + o_ctl))->lj_one_stage, 1, 4, s), LAMSA_HP_EKERNEL);          // (after the counters were zeroed)
     const PhaseArgs *da = (const PhaseArgs *)(d + o_args);
     HIPCHK(h, hipEventRecord(e0, s), LAMSA_HP_EKERNEL);
     hipLaunchKernelGGL(g_chain_shapes[Q.shape].k1, dim3(std::min(w_chain, n)), dim3(64), 0, s, da);
@@ -665,7 +682,7 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
         HIPCHK(h, hipEventRecord(Ln.ep[5], s), LAMSA_HP_EKERNEL);
         if (!g_nowave) hipLaunchKernelGGL(k_filldp_wave, dim3(w_wj), dim3(64), 0, s, da, 0);       // the long jobs first; the lane-per-job launch follows on the same stream (the two do not overlap)
         HIPCHK(h, hipEventRecord(Ln.ep[6], s), LAMSA_HP_EKERNEL);
-        if (!g_nolane) hipLaunchKernelGGL(k_filldp_small, dim3(w_dp), dim3(64), 0, s, da, 0);
+        if (!g_nolane) launch_filldp(g_lane_stages, w_dp, s, da, 0);
     } else { HIPCHK(h, hipEventRecord(Ln.ep[5], s), LAMSA_HP_EKERNEL); HIPCHK(h, hipEventRecord(Ln.ep[6], s), LAMSA_HP_EKERNEL); }
     HIPCHK(h, hipEventRecord(Ln.ep[4], s), LAMSA_HP_EKERNEL);
     hipLaunchKernelGGL(k_fill, dim3(w_fill), dim3(64), 0, s, da, 0);
@@ -673,10 +690,10 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
     hipLaunchKernelGGL(g_chain_shapes[Q.shape].k2, dim3(std::min(w_chain, n)), dim3(64), 0, s, da);
     HIPCHK(h, hipEventRecord(Ln.ep[2], s), LAMSA_HP_EKERNEL);
     if (list) {
-        HIPCHK(h, hipMemsetAsync(&((PhaseCtl *)(d + o_ctl))->q_head[5], 0, 16, s), LAMSA_HP_EKERNEL);          // the four queue heads of the listing and DP launches
+        HIPCHK(h, hipMemsetAsync(&((PhaseCtl *)(d + o_ctl))->q_head[5], 0, 20, s), LAMSA_HP_EKERNEL);          // the five queue heads of the listing and DP launches (5 .. 9)
         hipLaunchKernelGGL(k_filllist, dim3(w_fill), dim3(64), 0, s, da, 1);
         if (!g_nowave) hipLaunchKernelGGL(k_filldp_wave, dim3(w_wj), dim3(64), 0, s, da, 1);
-        if (!g_nolane) hipLaunchKernelGGL(k_filldp_small, dim3(w_dp), dim3(64), 0, s, da, 1);
+        if (!g_nolane) launch_filldp(g_lane_stages, w_dp, s, da, 1);
     }
     hipLaunchKernelGGL(k_fill, dim3(w_fill), dim3(64), 0, s, da, 1);
     HIPCHK(h, hipEventRecord(Ln.ep[3], s), LAMSA_HP_EKERNEL);
@@ -684,6 +701,9 @@ static int launch_phased(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, O
     HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
     HIPCHK(h, hipEventRecord(e1, s), LAMSA_HP_EKERNEL);
     Ln.phased = true;
+#ifdef HP_LJ_STATS
+    Ln.ctl_dev = (const PhaseCtl *)(d + o_ctl);
+#endif
     return LAMSA_HP_OK;
 }
 
@@ -780,6 +800,16 @@ static int finish_main(lamsa_hp_handle *h, AlignState *S, Slot &T, Slot &Ln, lam
         h->kernel_ms[16] = (float)dg[12]; h->kernel_ms[17] = (float)((double)dg[13] * 1e-6); h->kernel_ms[18] = (float)dg[14]; h->kernel_ms[19] = (float)((double)dg[15] * 4e-6); h->kernel_ms[20] = (float)((double)dg[16] * 1e-6);   // wave jobs, their algorithmic MB, lane jobs, MB of CIGARs computed ahead
 #ifdef HP_PROF
         prof_report(T, (const long long *)Ln.prof.p, n);
+#endif
+#ifdef HP_LJ_STATS
+        if (Ln.ctl_dev) {                                // diagnostic build (-DHP_LJ_STATS): the lane DP's counters of this batch (LJS_*, hp_phase.h), one line on stderr
+            unsigned long long v[LJS_N];
+            if (hipMemcpy(v, Ln.ctl_dev->lj_stat, sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
+                fprintf(stderr, "lj_stats stages=%d", g_lane_stages ? 1 : 0);
+                for (int k = 0; k < LJS_N; ++k) fprintf(stderr, " %llu", v[k]);
+                fprintf(stderr, "\n");
+            }
+        }
 #endif
     }
     // the per-read arrays are in mapped host memory already (OutDev); the slot may be reused while the caller still
@@ -969,5 +999,93 @@ extern "C" int lamsa_hp_set_result_tags(lamsa_hp_handle *h, int flags)
     AlignState *S = state_of(h);
     if (S->n_fifo || S->n_res) { h->err = "batches are in flight: collect them first"; return LAMSA_HP_EINVAL; }
     h->result_tags = flags;
+    return LAMSA_HP_OK;
+}
+
+// ---- lamsa_hp_dp_batch, kinds 12 / 13 (hp_api.hip hands them over): explicit jobs through the lane DP launches of the read path -- listed into the
+// queues as the lister would (kind and query class, in job order), then k_filldp_small stage by stage (LAMSA_HP_LANE_STAGES=0: in one launch).
+// 12 = a junction's ksw_bi_extend(100, 100), 13 = a seed gap's ksw_global2(band_w); w and h0 are not read.  Per job: status 0 = the CIGAR was published
+// (1: left to the fill), qle = the cells the job was charged, tle = 1 when it went through a hard queue.
+extern "C" int lamsa_hp_dp_batch_staged_(lamsa_hp_handle *h, const lamsa_hp_dp_jobs *J, lamsa_hp_dp_out *O)
+{
+    const int n = J->n_jobs;
+    if (!lj_params_ok(&h->para)) { h->err = "the handle's penalties do not keep the lane routines' 16-bit cells exact"; return LAMSA_HP_EINVAL; }
+    int64_t tot = 0;
+    for (int i = 0; i < n; ++i) {
+        if (J->kind[i] != 12 && J->kind[i] != 13) { h->err = "dp batch mixes job classes"; return LAMSA_HP_EINVAL; }
+        if (J->qlen[i] < 1 || J->qlen[i] > HP_LJ_QSMALL || J->tlen[i] < 0 || J->tlen[i] > HP_LJ_TSMALL) { h->err = "dp job beyond the lane routines' buffers"; return LAMSA_HP_EINVAL; }
+        if (J->q_off[i] < 0 || J->t_off[i] < 0 || J->q_off[i] + J->qlen[i] > J->seq_bytes || J->t_off[i] + J->tlen[i] > J->seq_bytes) { h->err = "dp job sequence out of range"; return LAMSA_HP_EINVAL; }
+        tot += J->tlen[i];
+    }
+    const int lj_cap = n + 1;
+    std::vector<uint8_t> pac((size_t)tot / 4 + 16, 0);
+    std::vector<LjRec> ljv((size_t)lj_cap); std::vector<int32_t> ljq((size_t)LJ_NBUCKET * lj_cap, -1);
+    PhaseCtl ctl; memset((void *)&ctl, 0, sizeof ctl);
+    ctl.lj_one_stage = g_lane_stages ? 0 : 1;
+    int64_t k = 0;
+    for (int i = 0; i < n; ++i) {
+        LjRec &R = ljv[i];
+        const int type = J->kind[i] - 11;
+        R.qaddr = J->q_off[i]; R.tk = k; R.slot = (int64_t)GS_WORDS * i; R.rd = i; R.tlen = (uint16_t)J->tlen[i]; R.qlen = (uint8_t)J->qlen[i]; R.type_comp = (int8_t)type;
+        for (int j = 0; j < J->tlen[i]; ++j, ++k) {
+            const uint8_t b = J->seq[J->t_off[i] + j];
+            if (b > 3) { h->err = "these routines read the target 2 bits per base: no N"; return LAMSA_HP_EINVAL; }
+            pac[(size_t)(k >> 2)] |= (uint8_t)(b << ((~k & 3) << 1));
+        }
+        const int b = lj_bucket_of(type, J->qlen[i]);
+        ljq[(size_t)b * lj_cap + ctl.lj_bucket_n[0][b]++] = i;
+        ++ctl.lj_n[0];
+    }
+    HIPCHK(h, hipSetDevice(h->device), LAMSA_HP_ENODEV);
+    const size_t slab_fill = al256(sizeof(cig_t) * 3 * HP_LJ_CIG * 64 + (size_t)HP_LJ_QSMALL * HP_LJ_TSMALL * 64 + 64);
+    const int w_dp = std::max(1, std::min((n + 63) / 64, h->n_cu * 2));
+    const int64_t job_cap = (int64_t)n * HP_LJ_CIG + 64;
+    size_t off = 0;
+    auto place = [&](size_t bytes) { size_t o = off; off = al256(off + bytes + 16); return o; };
+    const size_t o_args = place(sizeof(PhaseArgs)), o_ctl = place(sizeof(PhaseCtl)), o_meta = place(sizeof(RdMeta) * ((size_t)n + 1)), o_seq = place((size_t)J->seq_bytes), o_pac = place(pac.size()),
+                 o_lj = place(sizeof(LjRec) * (size_t)lj_cap), o_lq = place(4 * ljq.size()), o_fl = place(4 * (size_t)GS_WORDS * ((size_t)n + 1)), o_jb = place(4 * (size_t)job_cap), o_slab = place(slab_fill * (size_t)w_dp);
+    if (h->in.ensure(off)) { h->err = "hipMalloc(in)"; return LAMSA_HP_ENOMEM; }
+    char *d = (char *)h->in.p;
+    hipStream_t s = h->stream;
+    PhaseArgs a; memset((void *)&a, 0, sizeof a);
+    a.P = h->para; a.ctl = (PhaseCtl *)(d + o_ctl); a.in.read_seq = (const uint8_t *)(d + o_seq); a.ref.pac = (const uint8_t *)(d + o_pac); a.meta = (RdMeta *)(d + o_meta);
+    a.ljobs = (LjRec *)(d + o_lj); a.lj_bucket = (int32_t *)(d + o_lq); a.lj_cap = lj_cap; a.fl_base = (int32_t *)(d + o_fl); a.job_base = (int32_t *)(d + o_jb); a.job_cap = job_cap;
+    a.slab = d + o_slab; a.slab_fill = slab_fill; a.n_reads = n;
+    HIPCHK(h, hipMemsetAsync(d, 0, o_slab, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(d + o_args, &a, sizeof a, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(d + o_ctl, &ctl, sizeof ctl, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    if (J->seq_bytes > 0) HIPCHK(h, hipMemcpyAsync(d + o_seq, J->seq, (size_t)J->seq_bytes, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(d + o_pac, pac.data(), pac.size(), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(d + o_lj, ljv.data(), sizeof(LjRec) * ljv.size(), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(d + o_lq, ljq.data(), 4 * ljq.size(), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);                 // (the copies read pageable host memory of this frame)
+    HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+    if (n > 0) launch_filldp(g_lane_stages, w_dp, s, (const PhaseArgs *)(d + o_args), 0);
+    HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+    std::vector<int32_t> fl((size_t)GS_WORDS * ((size_t)n + 1)), jobs((size_t)job_cap); std::vector<RdMeta> meta((size_t)n + 1);
+    HIPCHK(h, hipMemcpyAsync(fl.data(), d + o_fl, 4 * fl.size(), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(jobs.data(), d + o_jb, 4 * jobs.size(), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync((void *)meta.data(), d + o_meta, sizeof(RdMeta) * meta.size(), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(ljq.data(), d + o_lq, 4 * ljq.size(), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(&ctl, d + o_ctl, sizeof ctl, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    hipEventElapsedTime(&h->kernel_ms[0], h->ev0, h->ev1);
+    h->h_score.assign((size_t)n, 0); h->h_qle.assign((size_t)n, 0); h->h_tle.assign((size_t)n, 0); h->h_status.assign((size_t)n, 0);
+    h->h_i64.assign((size_t)n + 1, 0); h->h_cig.clear();
+    for (int i = 0; i < n; ++i) {
+        const int32_t *slot = fl.data() + (size_t)GS_WORDS * i;
+        h->h_i64[i] = (int64_t)h->h_cig.size();
+        h->h_qle[i] = meta[i].cells; h->h_status[i] = slot[GS_HAS] ? 0 : 1;
+        if (slot[GS_HAS] && slot[GS_OFF] >= 0 && slot[GS_N] >= 0 && (int64_t)slot[GS_OFF] + slot[GS_N] <= job_cap) h->h_cig.insert(h->h_cig.end(), jobs.begin() + slot[GS_OFF], jobs.begin() + slot[GS_OFF] + slot[GS_N]);
+    }
+    h->h_i64[n] = (int64_t)h->h_cig.size();
+    for (int b = LJ_NORD; b < LJ_NBUCKET; ++b) {
+        const int nq = std::min(ctl.lj_bucket_n[0][b], lj_cap);
+        for (int q = 0; q < nq; ++q) { const int i = ljq[(size_t)b * lj_cap + q]; if (i >= 0 && i < n) h->h_tle[i] = 1; }
+    }
+    if (h->h_cig.empty()) h->h_cig.push_back(0);
+    O->score = h->h_score.data(); O->qle = h->h_qle.data(); O->tle = h->h_tle.data(); O->status = h->h_status.data();
+    O->cig_off = h->h_i64.data(); O->cigar = h->h_cig.data();
     return LAMSA_HP_OK;
 }

@@ -144,11 +144,13 @@ extern "C" const char *lamsa_hp_last_error(const lamsa_hp_handle *h) { return h 
 extern "C" float lamsa_hp_last_kernel_ms(const lamsa_hp_handle *h, int which) { return (h && which >= 0 && which < 24) ? h->kernel_ms[which] : -1.f; }
 
 
+extern "C" int lamsa_hp_dp_batch_staged_(lamsa_hp_handle *h, const lamsa_hp_dp_jobs *J, lamsa_hp_dp_out *O);      // kinds 12 / 13 (hp_align_api.hip)
 extern "C" int lamsa_hp_dp_batch(lamsa_hp_handle *h, const lamsa_hp_dp_jobs *J, lamsa_hp_dp_out *O)
 {
     if (!h || !J || !O || J->n_jobs < 0) return LAMSA_HP_EINVAL;
     HIPCHK(h, hipSetDevice(h->device), LAMSA_HP_ENODEV);
     const int n = J->n_jobs;
+    if (n > 0 && J->kind[0] >= 12) return lamsa_hp_dp_batch_staged_(h, J, O);
     // capacities: a DP CIGAR has at most qlen+tlen words (+ slack for the S/H pair of sw_mid_fix)
     std::vector<int64_t> cap_off((size_t)n + 1, 0);
     size_t z_need = 4096;

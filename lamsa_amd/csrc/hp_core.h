@@ -97,6 +97,9 @@ struct Ctx {
 //  90 / 91 hnode_dis on an insertion of split_len / 2 bases or more with ref_offset > 0 / == 0; largest values: 87 n_codes, 88 matches of a k-mer that was kept
 //  re-bases of the sliding window of ksw_extend_band (hp_ksw.h; tests/rebase_jobs.py), through HP_STATX_ADD / HP_STATX_MAX only: 92 re-bases, 95 / 96 those in the first / last row
 //  of a 64-row target block; largest values: 93 lanes freed by one re-base, 94 64 minus the lanes freed by one (so: 64 minus the fewest)
+//  the lane-per-job DP in two stages (hp_lanedp.h, phase_filldp of hp_phase.h; tests/lanedp_jobs.py), through HP_STATX_ADD only: 97 / 98 ksw_bi_extend / ksw_global2 jobs a first-stage
+//  or one-stage group ran, 99 .. 104 ksw_bi_extend jobs by exit (LJ_X_*: finished after the left extension, global after left, finished after the right extension, global after
+//  right, sw_mid_fix S-H, sw_mid_fix global), 105 jobs the first stage put into a hard queue, 106 jobs the second stage ran, 107 hard jobs left to the fill because their queue was full
 #ifndef HP_DPLOG
 #define HP_DPLOG(kind, qlen, tlen, w, cells) do { } while (0)      // tests' CPU build: one record per DP call (tools/dp_shapes.py)
 #endif
@@ -115,7 +118,7 @@ struct Ctx {
 // (HP_STAT_SLOTS, tests/emu/emu_api.cpp).  A CPU build whose array ends at slot 63 and the device build see an empty expression, so no slot is
 // ever written behind an array that was not made for it.
 #ifdef HP_STAT_SLOTS
-static_assert(HP_STAT_SLOTS >= 97, "the array of the path counters ends before the last slot the device sources use");
+static_assert(HP_STAT_SLOTS >= 108, "the array of the path counters ends before the last slot the device sources use");
 #define HP_STATX_ADD(i, n) HP_STAT_ADD(i, n)
 #define HP_STATX_MAX(i, v) HP_STAT_MAX(i, v)
 #else

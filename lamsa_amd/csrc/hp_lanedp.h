@@ -26,6 +26,12 @@ namespace hp {
 #define HP_LJ_LDS_WORDS(qcap) (((qcap) + 2) * 64 + ((qcap) + 2) * 16)
 #define HP_LJ_NEG (-20000)       // MINUS_INF of ksw_global2 in 16 bits: every comparison comes out as with -0x40000000 (see lj_params_ok)
 
+#ifdef HP_LJ_STATS
+#define LJ_PASS(J, k, n) ((J).pc[k] = (int)(n))
+#else
+#define LJ_PASS(J, k, n) ((void)(n))
+#endif
+
 struct LCig { cig_t *c; int n; };
 HP_INL void lc_push0(LCig &v, cig_t w) { if (v.n > 0 && (v.c[v.n - 1] & 0xf) == (w & 0xf)) v.c[v.n - 1] += (w >> 4) << 4; else v.c[v.n++] = w; }      // _push_cigar0
 HP_INL void lc_push1(LCig &v, cig_t w) { if ((w >> 4) != 0) lc_push0(v, w); }                                                                        // _push_cigar1
@@ -51,6 +57,10 @@ struct LaneJob {
     HP_L int32_t *row; HP_L uint8_t *qrow;   // this lane's cells in LDS: row[j * 64], qrow[j * 64]
     int rev;                                 // the query codes in qrow are stored for the reversed job (ksw_extend_r)
     long long cells;
+    int exit;                                // LJ_X_*: how lj_bi_left / lj_bi_extend ended (written by them only)
+#ifdef HP_LJ_STATS
+    int pc[5];                               // diagnostic build: cells of the DP passes of lj_bi_extend (left, global after left, right, global after right, sw_mid_fix's global)
+#endif
 };
 HP_INL int lj_qbase(const LaneJob &J, int j) { const int c = J.q[(long)j * J.qs]; return J.qcomp ? (c < 4 ? 3 - c : 4) : c; }
 HP_INL int lj_t(const LaneJob &J, int i) { const int64_t k = J.tk + (int64_t)i * J.ts; return J.pac[k >> 2] >> ((~k & 3) << 1) & 3; }      // _get_pac, bntseq.c:242
@@ -239,36 +249,60 @@ HP_INL int lj_extend(const lamsa_hp_para *P, LaneJob &J, int w, int h0, int *qle
     return max;
 }
 
+// How a ksw_bi_extend job ended, in the order the routine meets its exits (LaneJob::exit; path counters 99 .. 104 of hp_core.h in the
+// same order).  A wave runs the DP passes of every exit one of its 64 lanes takes; LJ_X_LEFT is the only one with a single pass.
+enum { LJ_X_LEFT = 0, LJ_X_LEFT_GLOBAL, LJ_X_RIGHT, LJ_X_RIGHT_GLOBAL, LJ_X_MID_SH, LJ_X_MID_GLOBAL, LJ_X_MORE };
+
+// ksw_bi_extend (src/ksw.c:862-926), first part: the left extension and, where it ends the job (res < 2, :875-880), the finished
+// CIGAR in `out` (LJ_X_LEFT).  Otherwise LJ_X_MORE: `out` stays empty, L holds the extension's CIGAR and lqe / lte where it ended.
+HP_INL int lj_bi_left(const lamsa_hp_para *P, LaneJob &J, int lh0, LCig &L, LCig &out, int *lqe, int *lte)
+{
+    const int qlen = J.qlen, tlen = J.tlen;
+    out.n = 0; L.n = 0;
+    const int w = iabs(qlen - tlen) + 3 > P->band_w ? iabs(qlen - tlen) + 3 : P->band_w;     // :873
+    const long long c0 = J.cells;
+    LJ_PASS(J, 1, 0); LJ_PASS(J, 2, 0); LJ_PASS(J, 3, 0); LJ_PASS(J, 4, 0);
+    lj_extend(P, J, w, lh0, lqe, lte, &L);
+    LJ_PASS(J, 0, J.cells - c0);
+    const int res = *lqe == qlen ? 0 : (*lte == tlen ? 1 : 2);                              // ksw_extend_c, :815-817
+    if (res == 2) { J.exit = LJ_X_MORE; return LJ_X_MORE; }
+    lc_pushv(out, L.c, L.n);
+    lc_push1(out, res == 0 ? ((tlen - *lte) << 4) | C_D : ((qlen - *lqe) << 4) | C_I);
+    J.exit = LJ_X_LEFT; HP_STATX_ADD(99, 1);
+    return LJ_X_LEFT;
+}
+
 // ksw_bi_extend (src/ksw.c:862-926) with sw_mid_fix (:841-860); qlen > 0.  L, R: scratch CIGARs of the lane.
 HP_INL int lj_bi_extend(const lamsa_hp_para *P, LaneJob &J, int lh0, int rh0, LCig &L, LCig &R, LCig &out)
 {
     const int qlen = J.qlen, tlen = J.tlen;
     int res, lqe, lte, rqe, rte;
-    out.n = 0; L.n = 0; R.n = 0;
+    R.n = 0;
     const int w = iabs(qlen - tlen) + 3 > P->band_w ? iabs(qlen - tlen) + 3 : P->band_w;     // :873
-    lj_extend(P, J, w, lh0, &lqe, &lte, &L);
-    res = lqe == qlen ? 0 : (lte == tlen ? 1 : 2);                                          // ksw_extend_c, :815-817
-    if (res < 2) {                                                                          // :875-880
-        lc_pushv(out, L.c, L.n);
-        lc_push1(out, res == 0 ? ((tlen - lte) << 4) | C_D : ((qlen - lqe) << 4) | C_I);
-        return 0;
-    }
+    if (lj_bi_left(P, J, lh0, L, out, &lqe, &lte) == LJ_X_LEFT) return 0;                   // :875-880
+    const long long c1 = J.cells;
     if (bi_near_diag(P, qlen, tlen) && ((lqe << 1 > qlen) || (lte << 1 > tlen))) {          // :881-887
         lj_global(P, J, P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, P->band_w, &out);
+        LJ_PASS(J, 1, J.cells - c1);
+        J.exit = LJ_X_LEFT_GLOBAL; HP_STATX_ADD(100, 1);
         return 0;
     }
     LaneJob Rj = lj_rev(J);
     lj_extend(P, Rj, w, rh0, &rqe, &rte, &R);
+    LJ_PASS(J, 2, Rj.cells - c1);
     J.cells = Rj.cells;
     res = rqe == qlen ? 0 : (rte == tlen ? 1 : 2);
     if (res < 2) {                                                                          // :892-899
         lc_push1(R, res == 0 ? ((tlen - rte) << 4) | C_D : ((qlen - rqe) << 4) | C_I);
         lc_invert(R);
         lc_pushv(out, R.c, R.n);
+        J.exit = LJ_X_RIGHT; HP_STATX_ADD(101, 1);
         return 0;
     }
     if (bi_near_diag(P, qlen, tlen) && ((rqe << 1 > qlen) || (rte << 1 > tlen))) {          // :900-906
         lj_global(P, J, P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, P->band_w, &out);
+        LJ_PASS(J, 3, J.cells - Rj.cells);
+        J.exit = LJ_X_RIGHT_GLOBAL; HP_STATX_ADD(102, 1);
         return 0;
     }
     lc_invert(R);
@@ -279,10 +313,13 @@ HP_INL int lj_bi_extend(const lamsa_hp_para *P, LaneJob &J, int lh0, int rh0, LC
             lc_push0(out, (cig_t)((uint32_t)Sn << 4) | C_S);
             lc_push0(out, (cig_t)((uint32_t)Hn << 4) | C_H);
             lc_pushv(out, R.c, R.n);
+            J.exit = LJ_X_MID_SH; HP_STATX_ADD(103, 1);
         } else {
             LCig g; g.c = L.c; g.n = 0;                                                     // L is not needed any more
             lj_global(P, J, P->del_gapo, P->del_gape, P->ins_gapo, P->ins_gape, P->band_w, &g);
+            LJ_PASS(J, 4, J.cells - Rj.cells);
             lc_pushv(out, g.c, g.n);
+            J.exit = LJ_X_MID_GLOBAL; HP_STATX_ADD(104, 1);
         }
     }
     return (qlen - lqe - rqe) >= P->split_len ? 1 : 0;                                      // :924
