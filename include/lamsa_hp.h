@@ -275,6 +275,37 @@ float lamsa_hp_last_kernel_ms(const lamsa_hp_handle *h, int which);
  * always.  For memory-constrained devices and for testing that second pass. */
 int lamsa_hp_set_scratch_limit(lamsa_hp_handle *h, size_t bytes);
 
+/* ------------------------------------------------------------------------------------
+ * The FM index of the reference's <ref>.bwt / <ref>.sa resident in HBM, and the batched exact search of k-mers in it: what
+ * bwt_match_exact_alt (src/bwt.c:241) and bwt_sa (:86) answer one call at a time, for a caller that has its seeds in a batch
+ * (stage 4, src/bwt_aln.c:316-363, is one).  The index is the text "forward reference + its reverse complement" of seq_len
+ * symbols; row 0 is the sentinel suffix, row r >= 1 the r-th smallest suffix, primary the row of suffix 0.
+ *   bwt, bwt_words   the words of <ref>.bwt behind its 40-byte header (blocks of 16: four 64-bit counts, 128 two-bit symbols);
+ *                    at least (seq_len + 15) / 16 + (seq_len + 127) / 128 * 8 of them
+ *   L2               L2[0] = 0 and the four cumulative counts of the header; L2[4] = seq_len
+ *   sa, n_sa         n_sa = (seq_len + sa_intv) / sa_intv samples, sa[j] the text position of row j * sa_intv: sa[0] = (uint64_t)-1
+ *                    (bwt_restore_sa, :440), then the values of <ref>.sa behind its 56-byte header; sa_intv a power of two
+ * lamsa_hp_fm_load copies the index to the device; it replaces an index loaded earlier and lamsa_hp_destroy frees it.  After a
+ * failed load the handle holds no index.  A handle created without a reference takes both calls.
+ * ---------------------------------------------------------------------------------- */
+typedef struct lamsa_hp_fm_index { uint64_t seq_len, primary, L2[5]; const uint32_t *bwt; uint64_t bwt_words;
+                                   const uint64_t *sa; uint64_t n_sa, sa_intv; } lamsa_hp_fm_index;
+int lamsa_hp_fm_load(lamsa_hp_handle *h, const lamsa_hp_fm_index *ix);
+/* Queries: window w holds base codes 0..4 at seq[win_off[w] .. win_off[w+1]); its k-mers are all len - k + 1 overlapping ones in
+ * order (none when the window is shorter than k), so k-mer j of the call is the (j - kmer_off[w])-th of its window.
+ * Results (callee-owned, valid until the next lamsa_hp_fm_search on the handle): lo[j] .. hi[j] the inclusive row interval of
+ * k-mer j, lo = 1, hi = 0 when it does not occur or holds a code above 3; for a k-mer with 1 <= hi - lo + 1 <= max_occ,
+ * pos[pos_off[j] + i] is the suffix-array value of row lo + i (a coordinate in the doubled text; strand, contig and bounds are the
+ * caller's), every other k-mer has none (pos_off[j + 1] == pos_off[j]).  max_occ = 0: intervals only.
+ * LAMSA_HP_EINVAL: no index loaded, k outside 1..255, max_occ outside 0..2^20, offsets that decrease or leave seq_bytes.
+ * The call blocks.  The device buffer for the positions is bounded: they are located and fetched in slices.
+ * lamsa_hp_last_kernel_ms 21 / 22 / 23: the search kernel, the locate kernel (all slices), the scan between them. */
+typedef struct lamsa_hp_fm_queries { int32_t n_win; const uint8_t *seq; int64_t seq_bytes; const int64_t *win_off; /* [n_win+1] */
+                                     int32_t k, max_occ; } lamsa_hp_fm_queries;
+typedef struct lamsa_hp_fm_out { int64_t n_kmers; const int64_t *kmer_off; /* [n_win+1] */ const uint64_t *lo, *hi; /* [n_kmers] */
+                                 const int64_t *pos_off; /* [n_kmers+1] */ const uint64_t *pos; } lamsa_hp_fm_out;
+int lamsa_hp_fm_search(lamsa_hp_handle *h, const lamsa_hp_fm_queries *q, lamsa_hp_fm_out *out);
+
 #ifdef __cplusplus
 }
 #endif

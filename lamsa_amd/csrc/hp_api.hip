@@ -7,6 +7,7 @@
 #include <string.h>
 #include <math.h>
 #include <vector>
+#include <algorithm>
 #include <string>
 #include "hp_dp_batch.h"
 #include "hp_wavejob.h"
@@ -132,6 +133,9 @@ extern "C" void lamsa_hp_destroy(lamsa_hp_handle *h)
     if (h->d_seq_off) hipFree(h->d_seq_off);
     if (h->d_seq_len) hipFree(h->d_seq_len);
     h->in.release(); h->out.release(); h->slab.release(); h->misc.release(); h->pac2.release();
+    if (h->fm_bwt) hipFree(h->fm_bwt);
+    if (h->fm_sa) hipFree(h->fm_sa);
+    h->fm_in.release(); h->fm_out.release(); h->fm_pos.release();
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -287,5 +291,145 @@ extern "C" int lamsa_hp_dp_batch(lamsa_hp_handle *h, const lamsa_hp_dp_jobs *J, 
     if (h->h_cig.empty()) h->h_cig.push_back(0);
     O->score = h->h_score.data(); O->qle = h->h_qle.data(); O->tle = h->h_tle.data(); O->status = h->h_status.data();
     O->cig_off = h->h_i64.data(); O->cigar = h->h_cig.data();
+    return LAMSA_HP_OK;
+}
+
+// ------------------------------------------------------------------ the resident FM index: lamsa_hp_fm_load / lamsa_hp_fm_search
+#include "hp_fm.h"
+
+// Plain grids, 256 lanes per workgroup, grid-strided beyond 2 048 workgroups (8 waves on every SIMD of 256 CUs).  Consecutive lanes take
+// consecutive k-mers / positions: a wave's query bytes are one stretch and its stores are coalesced.  No LDS; 64 VGPRs at the most.
+enum { FM_BLOCK = 256, FM_MAX_GRID = 2048 };
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_fm_search(FmSearchArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t j = (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; j < a.n_kmers; j += step) fm_search_lane(a, j);
+}
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_fm_locate(FmLocateArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t t = a.t0 + (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; t < a.t1; t += step) fm_locate_lane(a, t);
+}
+// the scan of the counts between the two: one wave per workgroup, a tile of HP_FM_TILE counts per wave
+__global__ __launch_bounds__(64) void k_fm_scan_sums(FmScanArgs a) { for (int64_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x) fm_scan_sums(a, t); }
+__global__ __launch_bounds__(64) void k_fm_scan_tiles(FmScanArgs a) { fm_scan_tiles(a); }
+__global__ __launch_bounds__(64) void k_fm_scan_write(FmScanArgs a) { for (int64_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x) fm_scan_write(a, t); }
+
+static void fm_drop(lamsa_hp_handle *h)
+{
+    if (h->fm_bwt) hipFree(h->fm_bwt);
+    if (h->fm_sa) hipFree(h->fm_sa);
+    h->fm_bwt = h->fm_sa = nullptr;
+}
+
+extern "C" int lamsa_hp_fm_load(lamsa_hp_handle *h, const lamsa_hp_fm_index *ix)
+{
+    if (!h) return LAMSA_HP_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device), LAMSA_HP_ENODEV);
+    fm_drop(h);                                               // whatever happens, the earlier index is gone
+    if (!ix || !ix->bwt || !ix->sa) { h->err = "fm index: null pointer"; return LAMSA_HP_EINVAL; }
+    bool ok = ix->seq_len > 0 && ix->seq_len < ((uint64_t)1 << 62) && ix->primary >= 1 && ix->primary <= ix->seq_len && ix->L2[0] == 0 && ix->L2[4] == ix->seq_len &&
+              ix->sa_intv > 0 && (ix->sa_intv & (ix->sa_intv - 1)) == 0;
+    for (int c = 0; ok && c < 4; ++c) ok = ix->L2[c] <= ix->L2[c + 1];
+    ok = ok && ix->bwt_words >= ((ix->seq_len + 15) >> 4) + ((ix->seq_len + 127) >> 7) * 8 && ix->bwt_words < ((uint64_t)1 << 60) &&
+         ix->n_sa == (ix->seq_len + ix->sa_intv) / ix->sa_intv;
+    if (!ok) { h->err = "fm index: sizes that contradict each other"; return LAMSA_HP_EINVAL; }
+    const size_t bb = (size_t)ix->bwt_words * 4, sb = (size_t)ix->n_sa * 8;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (bb + 64 > total_b || sb > total_b - (bb + 64))) { h->err = "fm index: larger than the device memory"; return LAMSA_HP_ENOMEM; }
+    // 64 bytes behind the words: the last block is read whole wherever the file ends inside it
+    if (hipMalloc(&h->fm_bwt, bb + 64) != hipSuccess) { h->fm_bwt = nullptr; (void)hipGetLastError(); h->err = "hipMalloc(fm bwt)"; return LAMSA_HP_ENOMEM; }
+    if (hipMalloc(&h->fm_sa, sb) != hipSuccess) { h->fm_sa = nullptr; (void)hipGetLastError(); fm_drop(h); h->err = "hipMalloc(fm sa)"; return LAMSA_HP_ENOMEM; }
+    if (hipMemset((char *)h->fm_bwt + bb, 0, 64) != hipSuccess || hipMemcpy(h->fm_bwt, ix->bwt, bb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->fm_sa, ix->sa, sb, hipMemcpyHostToDevice) != hipSuccess) { fm_drop(h); h->err = "fm index: copy to the device failed"; return LAMSA_HP_EKERNEL; }
+    h->fm_ix = *ix; h->fm_ix.bwt = nullptr; h->fm_ix.sa = nullptr;
+    return LAMSA_HP_OK;
+}
+
+extern "C" int lamsa_hp_fm_search(lamsa_hp_handle *h, const lamsa_hp_fm_queries *q, lamsa_hp_fm_out *out)
+{
+    if (!h || !q || !out) return LAMSA_HP_EINVAL;
+    if (!h->fm_bwt) { h->err = "fm search: no index loaded"; return LAMSA_HP_EINVAL; }
+    if (q->k < 1 || q->k > 255 || q->max_occ < 0 || q->max_occ > HP_FM_MAX_OCC || q->n_win < 0 || q->seq_bytes < 0 || (q->n_win > 0 && (!q->win_off || !q->seq))) { h->err = "fm search: k outside 1..255, max_occ outside 0..2^20 or a null array"; return LAMSA_HP_EINVAL; }
+    const int nw = q->n_win;
+    if (nw > 0 && q->win_off[0] < 0) { h->err = "fm search: negative window offset"; return LAMSA_HP_EINVAL; }
+    for (int w = 0; w < nw; ++w) if (q->win_off[w + 1] < q->win_off[w]) { h->err = "fm search: window offsets decrease"; return LAMSA_HP_EINVAL; }
+    if (nw > 0 && q->win_off[nw] > q->seq_bytes) { h->err = "fm search: window beyond seq_bytes"; return LAMSA_HP_EINVAL; }
+    HIPCHK(h, hipSetDevice(h->device), LAMSA_HP_ENODEV);
+    h->fm_kmer_off.assign((size_t)nw + 1, 0);
+    for (int w = 0; w < nw; ++w) { const int64_t len = q->win_off[w + 1] - q->win_off[w]; h->fm_kmer_off[(size_t)w + 1] = h->fm_kmer_off[(size_t)w] + (len >= q->k ? len - q->k + 1 : 0); }
+    const int64_t n = h->fm_kmer_off[(size_t)nw];
+    h->fm_lo.assign((size_t)n + 1, 0); h->fm_hi.assign((size_t)n + 1, 0); h->fm_pos_off.assign((size_t)n + 1, 0); h->fm_posv.assign(1, 0);
+    h->kernel_ms[21] = h->kernel_ms[22] = h->kernel_ms[23] = 0;
+    out->n_kmers = n; out->kmer_off = h->fm_kmer_off.data(); out->lo = h->fm_lo.data(); out->hi = h->fm_hi.data(); out->pos_off = h->fm_pos_off.data(); out->pos = h->fm_posv.data();
+    if (n == 0) return LAMSA_HP_OK;
+
+    const int64_t s0 = q->win_off[0], sbytes = q->win_off[nw] - s0;          // only the bytes the windows cover travel
+    const int64_t n_tiles = (n + HP_FM_TILE - 1) / HP_FM_TILE;
+    const size_t o_win = al256((size_t)sbytes + 16), o_koff = o_win + al256(8 * ((size_t)nw + 1)), in_bytes = o_koff + al256(8 * ((size_t)nw + 1));
+    const size_t o_hi = al256(8 * (size_t)n), o_cnt = 2 * o_hi, o_poff = o_cnt + al256(4 * (size_t)n), o_tsum = o_poff + al256(8 * ((size_t)n + 1)),
+                 o_toff = o_tsum + al256(4 * (size_t)n_tiles), out_bytes = o_toff + al256(8 * ((size_t)n_tiles + 1));
+    if (h->fm_in.ensure(in_bytes)) { (void)hipGetLastError(); h->err = "hipMalloc(fm in)"; return LAMSA_HP_ENOMEM; }
+    if (h->fm_out.ensure(out_bytes)) { (void)hipGetLastError(); h->err = "hipMalloc(fm out)"; return LAMSA_HP_ENOMEM; }
+    char *din = (char *)h->fm_in.p, *dout = (char *)h->fm_out.p;
+    hipStream_t s = h->stream;
+    std::vector<int64_t> woff((size_t)nw + 1);
+    for (int w = 0; w <= nw; ++w) woff[(size_t)w] = q->win_off[w] - s0;
+    HIPCHK(h, hipMemcpyAsync(din, q->seq + s0, (size_t)sbytes, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + o_win, woff.data(), 8 * ((size_t)nw + 1), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + o_koff, h->fm_kmer_off.data(), 8 * ((size_t)nw + 1), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+
+    FmIx ix;
+    ix.seq_len = h->fm_ix.seq_len; ix.primary = h->fm_ix.primary; for (int c = 0; c < 5; ++c) ix.L2[c] = h->fm_ix.L2[c];
+    ix.bwt = (const uint32_t *)h->fm_bwt; ix.sa = (const uint64_t *)h->fm_sa; ix.sa_intv = h->fm_ix.sa_intv;
+    FmSearchArgs a;
+    a.ix = ix; a.seq = (const uint8_t *)din; a.win_off = (const int64_t *)(din + o_win); a.kmer_off = (const int64_t *)(din + o_koff);
+    a.n_win = nw; a.k = q->k; a.max_occ = q->max_occ; a.n_kmers = n;
+    a.lo = (uint64_t *)dout; a.hi = (uint64_t *)(dout + o_hi); a.cnt = (int32_t *)(dout + o_cnt);
+    auto grid_of = [](int64_t items) { const int64_t g = (items + FM_BLOCK - 1) / FM_BLOCK; return dim3((unsigned)(g < FM_MAX_GRID ? g : FM_MAX_GRID)); };
+    HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+    hipLaunchKernelGGL(k_fm_search, grid_of(n), dim3(FM_BLOCK), 0, s, a);
+    HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(h->fm_lo.data(), a.lo, 8 * (size_t)n, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(h->fm_hi.data(), a.hi, 8 * (size_t)n, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    hipEventElapsedTime(&h->kernel_ms[21], h->ev0, h->ev1);
+    if (q->max_occ == 0) return LAMSA_HP_OK;
+
+    // counts -> offsets on the device; the host only learns the offsets it hands out anyway
+    FmScanArgs sc;
+    sc.cnt = a.cnt; sc.n = n; sc.n_tiles = n_tiles; sc.tile_sum = (int32_t *)(dout + o_tsum); sc.tile_off = (int64_t *)(dout + o_toff); sc.pos_off = (int64_t *)(dout + o_poff);
+    const dim3 sgrid((unsigned)(n_tiles < 8 * FM_MAX_GRID ? n_tiles : 8 * FM_MAX_GRID));
+    HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+    hipLaunchKernelGGL(k_fm_scan_sums, sgrid, dim3(64), 0, s, sc);
+    hipLaunchKernelGGL(k_fm_scan_tiles, dim3(1), dim3(64), 0, s, sc);
+    hipLaunchKernelGGL(k_fm_scan_write, sgrid, dim3(64), 0, s, sc);
+    HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(h->fm_pos_off.data(), sc.pos_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    hipEventElapsedTime(&h->kernel_ms[23], h->ev0, h->ev1);
+    const int64_t total = h->fm_pos_off[(size_t)n];
+    if (total < 0 || total > n * (int64_t)q->max_occ) { h->err = "fm search: the device scan went wrong"; return LAMSA_HP_EKERNEL; }
+    h->fm_posv.assign((size_t)total + 1, 0);
+    out->pos = h->fm_posv.data();
+
+    // rows -> text positions, a slice of the flat position list at a time: the device buffer stays bounded whatever n * max_occ is
+    const int64_t slice = getenv("LAMSA_HP_FM_SLICE") ? std::max<int64_t>(1, atoll(getenv("LAMSA_HP_FM_SLICE"))) : ((int64_t)4 << 20);      // 32 MB of positions (tests lower it)
+    if (total > 0 && h->fm_pos.ensure(8 * (size_t)std::min(slice, total))) { (void)hipGetLastError(); h->err = "hipMalloc(fm pos)"; return LAMSA_HP_ENOMEM; }
+    FmLocateArgs la;
+    la.ix = ix; la.lo = a.lo; la.pos_off = sc.pos_off; la.n_kmers = n; la.pos = (uint64_t *)h->fm_pos.p;
+    for (int64_t t0 = 0; t0 < total; t0 += slice) {
+        la.t0 = t0; la.t1 = std::min(total, t0 + slice);
+        HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+        hipLaunchKernelGGL(k_fm_locate, grid_of(la.t1 - la.t0), dim3(FM_BLOCK), 0, s, la);
+        HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipMemcpyAsync(h->fm_posv.data() + t0, la.pos, 8 * (size_t)(la.t1 - la.t0), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+        float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
+        h->kernel_ms[22] += ms;
+    }
     return LAMSA_HP_OK;
 }

@@ -40,6 +40,10 @@ struct lamsa_hp_handle {
     float kernel_ms[24] = {0};
     size_t scratch_limit = 0;      // lamsa_hp_set_scratch_limit
     int result_tags = 0;           // lamsa_hp_set_result_tags: LAMSA_HP_TAG_* items of the result streams of later batches
+    // lamsa_hp_fm_load / lamsa_hp_fm_search: the resident FM index, the buffers of a search and its callee-owned results
+    void *fm_bwt = nullptr, *fm_sa = nullptr; lamsa_hp_fm_index fm_ix = {};      // fm_ix: sizes and counts (its pointers are not kept); fm_bwt == nullptr: no index
+    DevBuf fm_in, fm_out, fm_pos;
+    std::vector<int64_t> fm_kmer_off, fm_pos_off; std::vector<uint64_t> fm_lo, fm_hi, fm_posv;
     std::string err;
 };
 

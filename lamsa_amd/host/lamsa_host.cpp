@@ -15,6 +15,9 @@
 // referenced weakly: a C-ABI without it (the tests' CPU emulation of the library) leaves it null, and --MD then derives the mismatch
 // lists on the host with the walk of the stage-4 records (rec_aux); the product's library always has it and the device lists them
 #pragma weak lamsa_hp_set_result_tags
+// likewise the resident FM index: without the two calls --rescue-gpu says so and stage 4 searches on the host as it does by default
+#pragma weak lamsa_hp_fm_load
+#pragma weak lamsa_hp_fm_search
 #include <algorithm>
 #include <atomic>
 #include <cctype>
@@ -1276,12 +1279,25 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
         if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_set_result_tags failed: %d %s\n", e, lamsa_hp_last_error(hh)); for (lamsa_hp_handle *x : hs) lamsa_hp_destroy(x); return 2; }
     }
     // stage (4): needs the reference's FM index files and a second handle for its DP batches (a handle is single-threaded)
-    FmIndex fm; lamsa_hp_handle *h_dp = nullptr; bool rescue = false; long n_rescue_jobs = 0;
+    FmIndex fm; lamsa_hp_handle *h_dp = nullptr; bool rescue = false; long n_rescue_jobs = 0, n_rescue_kmers = 0;
     if (P.bwt_max_len > 0 && !opt.parse_only) {
         std::string e2;
         if (!fm.load(opt.ref_prefix, e2)) fprintf(stderr, "[lamsa_aln] note: stage 4 (BWT rescue of uncovered regions <= -R %d bp) is skipped: %s; output equals the reference's with -R 0\n", P.bwt_max_len, e2.c_str());
         else if (lamsa_hp_create(&h_dp, &P, nullptr, devs[0]) != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] cannot create the stage-4 handle\n"); for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh); return 2; }
         else rescue = true;
+    }
+    // --rescue-gpu: the index goes into the stage-4 handle once; every chunk's windows are then searched there in one call
+    bool rescue_gpu = false;
+    if (rescue && opt.rescue_gpu) {
+        if (lamsa_hp_fm_load == nullptr || lamsa_hp_fm_search == nullptr) fprintf(stderr, "[lamsa_aln] note: --rescue-gpu: this library has no lamsa_hp_fm_load / lamsa_hp_fm_search; stage 4 searches on the host\n");
+        else {
+            lamsa_hp_fm_index fx; memset(&fx, 0, sizeof fx);
+            fx.seq_len = fm.seq_len; fx.primary = fm.primary; for (int c = 0; c < 5; ++c) fx.L2[c] = fm.L2[c];
+            fx.bwt = fm.bwt.data(); fx.bwt_words = (uint64_t)fm.bwt.size() - 4; fx.sa = fm.sa.data(); fx.n_sa = fm.n_sa; fx.sa_intv = fm.sa_intv;      // (FmIndex::load keeps 4 spare words)
+            const int e = lamsa_hp_fm_load(h_dp, &fx);
+            if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_load failed: %d %s\n", e, lamsa_hp_last_error(h_dp)); lamsa_hp_destroy(h_dp); for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh); return 2; }
+            rescue_gpu = true;
+        }
     }
     const double load_s = now_s() - t_begin;
     std::string sam;
@@ -1501,6 +1517,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
         if (RR.size() < (size_t)n) RR.resize((size_t)n);
         std::vector<RescuePlan> plans(rescue ? (size_t)n : 0);
         std::vector<RescueJobs> tj((size_t)threads);
+        std::vector<RescueWindows> tw(rescue_gpu ? (size_t)threads : 0);      // --rescue-gpu: the windows every thread lists
         std::vector<int> t_first((size_t)threads, 0), t_last((size_t)threads, 0);
         std::vector<long> bad_of((size_t)threads, 0);
         parallel_blocks(n, threads, [&](int t, int r0, int r1) {
@@ -1510,9 +1527,39 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 const int L = (int)B.reads[(size_t)r].seq.size();
                 parse_stream(res.stream + res.read_off[r], res.read_len[r], L, R, dev_tags);
                 read_finish(R, codes + roff[r], L, ix, what);
-                if (rescue && R.status == 0) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
+                if (rescue && R.status == 0 && !rescue_gpu) rescue_plan(R, codes + roff[r], L, ix, fm, P, plans[(size_t)r], tj[(size_t)t]);
+                else if (rescue && R.status == 0) rescue_windows(R, codes + roff[r], L, P, plans[(size_t)r], tw[(size_t)t]);
             }
         });
+        if (rescue_gpu) {
+            // the windows of all threads as one search on the stage-4 handle, then seeds -> chains -> jobs on the threads again
+            std::vector<int64_t> wbase((size_t)threads + 1, 0);
+            RescueWindows all;
+            all.win_off.push_back(0);
+            for (int t = 0; t < threads; ++t) {
+                const RescueWindows &w = tw[(size_t)t];
+                const int64_t s0 = (int64_t)all.seq.size();
+                for (size_t k = 1; k < w.win_off.size(); ++k) all.win_off.push_back(w.win_off[k] + s0);
+                all.seq.insert(all.seq.end(), w.seq.begin(), w.seq.end());
+                wbase[(size_t)t + 1] = (int64_t)all.win_off.size() - 1;
+            }
+            lamsa_hp_fm_queries fq; memset(&fq, 0, sizeof fq);
+            fq.n_win = (int32_t)(all.win_off.size() - 1); fq.seq = all.seq.data(); fq.seq_bytes = (int64_t)all.seq.size(); fq.win_off = all.win_off.data();
+            fq.k = P.bwt_seed_len; fq.max_occ = 500;                        // 5 * MAX_HIT (rescue.cpp): a seed with more rows is not located
+            lamsa_hp_fm_out found; memset(&found, 0, sizeof found);
+            const int e = lamsa_hp_fm_search(h_dp, &fq, &found);
+            if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_search (stage 4) failed: %d %s\n", e, lamsa_hp_last_error(h_dp)); return 2; }
+            n_rescue_kmers += found.n_kmers;
+            std::atomic<int> bad_found(0);
+            parallel_blocks(n, threads, [&](int t, int r0, int r1) {
+                for (int r = r0; r < r1; ++r) {
+                    const ReadResult &R = RR[(size_t)r];
+                    if (R.status != 0) continue;
+                    if (!rescue_plan_found(codes + roff[r], (int)B.reads[(size_t)r].seq.size(), ix, found, wbase[(size_t)t], P, plans[(size_t)r], tj[(size_t)t])) bad_found = 1;
+                }
+            });
+            if (bad_found.load()) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_search (stage 4) answered other windows than it was asked\n"); return 2; }
+        }
         const double t2 = now_s();
         // the DP jobs of all threads as one batch
         std::vector<int64_t> base((size_t)threads + 1, 0);

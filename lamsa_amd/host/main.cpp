@@ -41,7 +41,9 @@ static int usage()
                     "         block length, mapQ, tp:A:P NM:i AS:i de:f -- and one tp:A:S line per XA:Z alternative behind its record; no header, no line for an unmapped read;\n"
                     "         the GPU ships a fixed summary per record in place of its CIGAR; not with --SA, --MD, --cs, --eqx; --left-align changes nothing),\n"
                     "         --paf-cg (the same lines with cg:Z, the record's CIGAR without its clips, from the ordinary result stream: honours --eqx, --left-align,\n"
-                    "         --MD and --cs as SAM does; not with --SA or --paf)\n\n");
+                    "         --MD and --cs as SAM does; not with --SA or --paf),\n"
+                    "         --rescue-gpu (stage 4: the exact search of the -k mers of all uncovered regions of a chunk in one call on the GPU, in an FM index\n"
+                    "         kept in its memory, instead of one query at a time on the host threads; same output; nothing to do with -R 0)\n\n");
     return 1;
 }
 
@@ -72,7 +74,7 @@ int main(int argc, char *argv[])
         {"max-skel",1,0,'s'},{"max-reg",1,0,'R'},{"bwt-kmer",1,0,'k'},{"fastest",0,0,'f'},{"ed-rate",1,0,'e'},{"diff-rate",1,0,'d'},
         {"mis-rate",1,0,'x'},{"read-type",1,0,'T'},{"match-sc",1,0,'m'},{"mis-pen",1,0,'M'},{"open-pen",1,0,'O'},{"ext-pen",1,0,'E'},
         {"band-width",1,0,'w'},{"end-bonus",1,0,'b'},{"max-out",1,0,'r'},{"gap-split",1,0,'g'},{"soft-clip",0,0,'S'},{"comment",0,0,'C'},
-        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{"left-align",0,0,1014},{"paf",0,0,1015},{"paf-cg",0,0,1016},{0,0,0,0}};
+        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{"left-align",0,0,1014},{"paf",0,0,1015},{"paf-cg",0,0,1016},{"rescue-gpu",0,0,1017},{0,0,0,0}};
     optind = 2;
     while ((c = getopt_long(argc, argv, "t:l:i:p:V:v:s:R:k:fm:M:O:E:w:b:e:d:x:T:r:g:SCo:hHNI", lopt, NULL)) >= 0) {
         switch (c) {
@@ -127,6 +129,7 @@ int main(int argc, char *argv[])
             case 1014: opt.left_align = 1; break;
             case 1015: opt.paf = 1; break;
             case 1016: opt.paf_cg = 1; break;
+            case 1017: opt.rescue_gpu = 1; break;
             case 1007: { opt.devices.clear(); for (const char *q = optarg; *q;) { opt.devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; } break; }
         case 1001: opt.seed_result = optarg; break;
         case 1002: opt.chunk_reads = atoi(optarg) > 0 ? atoi(optarg) : opt.chunk_reads; break;

@@ -112,8 +112,8 @@ uint64_t FmIndex::match(int len, const uint8_t *s, uint64_t *k0, uint64_t *l0) c
 
 // ------------------------------------------------------------------ regions (get_reg / get_remain_reg)
 namespace {
-struct RegB { int is_rev, chr; int64_t pos; };
-struct Reg { int beg, end; std::vector<RegB> rb, re; };
+typedef RescueAnchor RegB;
+typedef RescueRegion Reg;
 
 int ref_in_cigar(const std::vector<int32_t> &c)
 {   // refInCigar, src/frag_check.c:205 (H counts as reference there)
@@ -246,129 +246,176 @@ static bool fetch_ref(const Index &ix, int chr, int64_t start0, int *len, std::v
     return true;
 }
 
-void rescue_plan(const ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const FmIndex &fm, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs)
+// Where the exact hits of a region's seeds come from.  find(i): how many rows seed i (the k-mer at offset i of the region) has, 0 for none;
+// at(m): the suffix-array value of its m-th row, asked in row order and only for a seed of at most 5 * MAX_HIT rows.
+namespace {
+struct HostSeeds {                   // the host FmIndex, one query at a time, a row located when it is asked for (bwt_match_exact_alt / bwt_sa)
+    const FmIndex &fm; const uint8_t *s; int k; uint64_t lo;
+    uint64_t find(int i) { uint64_t a = 0, l = fm.seq_len; if (!fm.match(k, s + i, &a, &l)) return 0; lo = a; return l - a + 1; }
+    uint64_t at(uint64_t m) const { return fm.sa_at(lo + m); }
+};
+struct FoundSeeds {                  // the answers of one lamsa_hp_fm_search for the window of the region
+    const lamsa_hp_fm_out &o; int64_t j0, j;
+    uint64_t find(int i) { j = j0 + i; return o.hi[j] >= o.lo[j] ? o.hi[j] - o.lo[j] + 1 : 0; }
+    uint64_t at(uint64_t m) const { return o.pos[o.pos_off[j] + (int64_t)m]; }
+};
+
+// seeds -> chains -> DP jobs of one region (bwt_aln_core :306)
+template <class Seeds> void plan_region(int ri, const Reg &reg, Seeds &src, const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs)
 {
-    plan.lines.clear(); plan.region_of.clear();
-    std::vector<Reg> regs, remain;
-    collect_regs(R, regs);
-    remain_regs(regs, read_len, P.bwt_seed_len, P.bwt_min_len, P.bwt_max_len, remain);
     const int seed_len = P.bwt_seed_len;
-    for (size_t ri = 0; ri < remain.size(); ++ri) {
-        const Reg &reg = remain[ri];
-        const int reg_beg = reg.beg, reg_len = reg.end - reg_beg + 1, seed_n = reg_len - seed_len + 1;
-        if (seed_n <= 0) continue;
-        std::vector<Seed> sv((size_t)seed_n);
-        // exact seeds (bwt_aln_core :316-363)
-        for (int i = 0; i < seed_n; ++i) {
-            sv[(size_t)i].pos = i + 1;
-            uint64_t k = 0, l = fm.seq_len;
-            if (!fm.match(seed_len, bseq + reg_beg - 1 + i, &k, &l)) continue;
-            const uint64_t cnt = l - k + 1;
-            if (cnt > 5 * (uint64_t)MAX_HIT) continue;
-            int kept = 0;
-            for (uint64_t m = k; m <= l; ++m) {
-                const uint64_t rp = fm.sa_at(m);
-                const int is_rev = (int64_t)rp >= ix.l_pac;
-                const int64_t pos = is_rev ? (ix.l_pac << 1) - 1 - (int64_t)rp : (int64_t)rp;
-                const int ref_id = pos2rid(ix, pos);
-                if (ref_id < 0) continue;
-                const int64_t sp = pos - ix.off[(size_t)ref_id] + 1 - (is_rev ? seed_len - 1 : 0);
-                if (sp + seed_len - 1 > ix.len[(size_t)ref_id] || sp < 0) continue;
-                if (cnt <= (uint64_t)MAX_HIT) set_seed(sv[(size_t)i], ref_id, is_rev, sp);
-                else {                                          // many hits: only those near an anchor of the region, at most 100
-                    if (!near_anchor(reg, ref_id, is_rev, sp, P.SV_len_thd)) continue;
-                    set_seed(sv[(size_t)i], ref_id, is_rev, sp);
-                    if (++kept == MAX_HIT) break;
-                }
+    const int reg_beg = reg.beg, reg_len = reg.end - reg_beg + 1, seed_n = reg_len - seed_len + 1;
+    if (seed_n <= 0) return;
+    std::vector<Seed> sv((size_t)seed_n);
+    // exact seeds (bwt_aln_core :316-363)
+    for (int i = 0; i < seed_n; ++i) {
+        sv[(size_t)i].pos = i + 1;
+        const uint64_t cnt = src.find(i);
+        if (cnt == 0 || cnt > 5 * (uint64_t)MAX_HIT) continue;
+        int kept = 0;
+        for (uint64_t m = 0; m < cnt; ++m) {
+            const uint64_t rp = src.at(m);
+            const int is_rev = (int64_t)rp >= ix.l_pac;
+            const int64_t pos = is_rev ? (ix.l_pac << 1) - 1 - (int64_t)rp : (int64_t)rp;
+            const int ref_id = pos2rid(ix, pos);
+            if (ref_id < 0) continue;
+            const int64_t sp = pos - ix.off[(size_t)ref_id] + 1 - (is_rev ? seed_len - 1 : 0);
+            if (sp + seed_len - 1 > ix.len[(size_t)ref_id] || sp < 0) continue;
+            if (cnt <= (uint64_t)MAX_HIT) set_seed(sv[(size_t)i], ref_id, is_rev, sp);
+            else {                                          // many hits: only those near an anchor of the region, at most 100
+                if (!near_anchor(reg, ref_id, is_rev, sp, P.SV_len_thd)) continue;
+                set_seed(sv[(size_t)i], ref_id, is_rev, sp);
+                if (++kept == MAX_HIT) break;
             }
-        }
-        // chain (bwt_update_dp :74): the nearest earlier seed hit within one base of the diagonal
-        for (int i = 1; i < seed_n; ++i)
-            for (Loc &a : sv[(size_t)i].loc) {
-                bool done = false;
-                for (int m = i - 1; m >= 0 && !done; --m)
-                    for (size_t n = 0; n < sv[(size_t)m].loc.size(); ++n) {
-                        const Loc &b = sv[(size_t)m].loc[n];
-                        if (a.is_rev != b.is_rev || a.ref_id != b.ref_id) continue;
-                        const int dis = (int)((a.is_rev ? -1 : 1) * (a.ref_pos - b.ref_pos) - (sv[(size_t)i].pos - sv[(size_t)m].pos));
-                        if (abs(dis) > 1) continue;
-                        a.from_x = m; a.from_y = (int)n; a.score = b.score + 1; a.NM = b.NM + abs(dis); a.node_n = b.node_n + 1;
-                        done = true; break;
-                    }
-            }
-        // chain ends (bwt_backtrack :97)
-        Heap hp; hp.max_n = P.res_mul_max;
-        int max_score = 0;
-        for (int i = seed_n - 1; i >= 0; --i)
-            for (size_t j = 0; j < sv[(size_t)i].loc.size(); ++j) {
-                Loc &a = sv[(size_t)i].loc[j];
-                if (a.track) continue;
-                if (near_anchor(reg, a.ref_id, a.is_rev, a.ref_pos, P.SV_len_thd)) a.score += a.score / 2;
-                if (a.score > max_score) { max_score = a.score; hp.add(i, (int)j, max_score, a.NM); }
-                else if (a.score >= max_score / 2) hp.add(i, (int)j, a.score, a.NM);
-                for (int fx = i, fy = (int)j; fx != -1;) { Loc &t = sv[(size_t)fx].loc[(size_t)fy]; t.track = 1; const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
-            }
-        std::vector<std::vector<std::pair<int, int>>> lines;
-        while (!hp.x.empty()) {                                 // node_pop takes the LAST array element, not the heap top
-            const int rx = hp.x.back(), ry = hp.y.back();
-            hp.x.pop_back(); hp.y.pop_back(); hp.score.pop_back(); hp.NM.pop_back();
-            if (sv[(size_t)rx].loc[(size_t)ry].score < max_score / 2) continue;
-            bool used = false;
-            for (int fx = rx, fy = ry; fx != -1;) { const Loc &t = sv[(size_t)fx].loc[(size_t)fy]; if (t.track == 2) { used = true; break; } const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
-            if (used) continue;
-            std::vector<std::pair<int, int>> ln((size_t)sv[(size_t)rx].loc[(size_t)ry].node_n);
-            int i = (int)ln.size() - 1;
-            for (int fx = rx, fy = ry; fx != -1; --i) { Loc &t = sv[(size_t)fx].loc[(size_t)fy]; if (i >= 0) ln[(size_t)i] = {fx, fy}; t.track = 2; const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
-            lines.push_back(std::move(ln));
-        }
-        // one alignment per chain (bwt_set_bound :183, bwt_aln_res :200-246)
-        for (const auto &ln : lines) {
-            RescueLine L;
-            const Loc &first = sv[(size_t)ln.front().first].loc[(size_t)ln.front().second], &last = sv[(size_t)ln.back().first].loc[(size_t)ln.back().second];
-            const int pos_first = sv[(size_t)ln.front().first].pos, pos_last = sv[(size_t)ln.back().first].pos;
-            L.ref_id = first.ref_id; L.is_rev = first.is_rev; L.reg_beg = reg_beg; L.reg_len = reg_len;
-            if (first.is_rev) {
-                L.right.read_pos = reg_len + 1 - pos_first; L.left.read_pos = reg_len + 1 - (pos_last + seed_len - 1);
-                L.right.ref_pos = first.ref_pos + seed_len - 1; L.left.ref_pos = last.ref_pos;
-            } else {
-                L.left.read_pos = pos_first; L.right.read_pos = pos_last + seed_len - 1;
-                L.left.ref_pos = first.ref_pos; L.right.ref_pos = last.ref_pos + seed_len - 1;
-            }
-            const int ext = 100;
-            const int after = read_len - (reg_beg + reg_len - 1), before = reg_beg - 1;
-            if (L.is_rev) { L.left_eta = after > ext ? ext : after; L.extra_end = reg_beg + reg_len + L.left_eta - 1; L.right_eta = before > ext ? ext : before; L.extra_beg = reg_beg - L.right_eta; }
-            else { L.left_eta = before > ext ? ext : before; L.extra_beg = reg_beg - L.left_eta; L.right_eta = after > ext ? ext : after; L.extra_end = reg_beg + reg_len + L.right_eta - 1; }
-            const int extra_len = reg_len + L.left_eta + L.right_eta;
-            L.query.resize((size_t)extra_len);
-            for (int i = 0; i < extra_len; ++i) {
-                const uint8_t c = bseq[L.extra_beg - 1 + i];
-                if (L.is_rev) L.query[(size_t)(extra_len - 1 - i)] = c < 4 ? 3 - c : 4; else L.query[(size_t)i] = c;
-            }
-            const int64_t want = L.left.ref_pos - (L.left.read_pos - 1 + L.left_eta) - seed_len;
-            L.ref_start = want < 1 ? 1 : want;
-            L.ref_len = (int)(L.right.ref_pos + reg_len - L.right.read_pos + L.right_eta + seed_len - L.ref_start + 1);
-            if (L.ref_len < 0 || !fetch_ref(ix, L.ref_id + 1, L.ref_start - 1, &L.ref_len, L.target)) continue;      // the reference exits here
-            const int mq = L.right.read_pos - L.left.read_pos + 1, mt = (int)(L.right.ref_pos - L.left.ref_pos + 1);
-            const int64_t t0 = L.left.ref_pos - L.ref_start;
-            if (mq < 0 || mt < 0 || t0 < 0 || t0 + mt > L.ref_len) continue;
-            L.job_mid = jobs.add(L.query.data() + (L.left.read_pos - 1 + L.left_eta), mq, L.target.data() + t0, mt, 0, P.band_w, 0);
-            if (L.left.read_pos > 1 || L.left_eta > 0) {
-                L.left_qlen = L.left.read_pos - 1 + L.left_eta;
-                const int tl = (int)t0;
-                L.lq.resize((size_t)L.left_qlen); L.lt.resize((size_t)tl);
-                for (int i = 0; i < L.left_qlen; ++i) L.lq[(size_t)i] = L.query[(size_t)(L.left_qlen - 1 - i)];
-                for (int i = 0; i < tl; ++i) L.lt[(size_t)i] = L.target[(size_t)(tl - 1 - i)];
-                L.job_left = jobs.add(L.lq.data(), L.left_qlen, L.lt.data(), tl, 1, P.band_w, seed_len * P.match);
-            }
-            if (L.right.read_pos < reg_len || L.right_eta > 0) {
-                L.right_qlen = reg_len - L.right.read_pos + L.right_eta;
-                const int64_t tl = L.ref_start + L.ref_len - 1 - L.right.ref_pos;
-                if (tl < 0 || tl > L.ref_len) continue;         // ksw_extend_core exits on a negative length
-                L.job_right = jobs.add(L.query.data() + L.right.read_pos + L.left_eta, L.right_qlen, L.target.data() + (L.ref_len - tl), (int)tl, 1, P.band_w, seed_len * P.match);
-            }
-            plan.lines.push_back(std::move(L)); plan.region_of.push_back((int)ri);
         }
     }
+    // chain (bwt_update_dp :74): the nearest earlier seed hit within one base of the diagonal
+    for (int i = 1; i < seed_n; ++i)
+        for (Loc &a : sv[(size_t)i].loc) {
+            bool done = false;
+            for (int m = i - 1; m >= 0 && !done; --m)
+                for (size_t n = 0; n < sv[(size_t)m].loc.size(); ++n) {
+                    const Loc &b = sv[(size_t)m].loc[n];
+                    if (a.is_rev != b.is_rev || a.ref_id != b.ref_id) continue;
+                    const int dis = (int)((a.is_rev ? -1 : 1) * (a.ref_pos - b.ref_pos) - (sv[(size_t)i].pos - sv[(size_t)m].pos));
+                    if (abs(dis) > 1) continue;
+                    a.from_x = m; a.from_y = (int)n; a.score = b.score + 1; a.NM = b.NM + abs(dis); a.node_n = b.node_n + 1;
+                    done = true; break;
+                }
+        }
+    // chain ends (bwt_backtrack :97)
+    Heap hp; hp.max_n = P.res_mul_max;
+    int max_score = 0;
+    for (int i = seed_n - 1; i >= 0; --i)
+        for (size_t j = 0; j < sv[(size_t)i].loc.size(); ++j) {
+            Loc &a = sv[(size_t)i].loc[j];
+            if (a.track) continue;
+            if (near_anchor(reg, a.ref_id, a.is_rev, a.ref_pos, P.SV_len_thd)) a.score += a.score / 2;
+            if (a.score > max_score) { max_score = a.score; hp.add(i, (int)j, max_score, a.NM); }
+            else if (a.score >= max_score / 2) hp.add(i, (int)j, a.score, a.NM);
+            for (int fx = i, fy = (int)j; fx != -1;) { Loc &t = sv[(size_t)fx].loc[(size_t)fy]; t.track = 1; const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
+        }
+    std::vector<std::vector<std::pair<int, int>>> lines;
+    while (!hp.x.empty()) {                                 // node_pop takes the LAST array element, not the heap top
+        const int rx = hp.x.back(), ry = hp.y.back();
+        hp.x.pop_back(); hp.y.pop_back(); hp.score.pop_back(); hp.NM.pop_back();
+        if (sv[(size_t)rx].loc[(size_t)ry].score < max_score / 2) continue;
+        bool used = false;
+        for (int fx = rx, fy = ry; fx != -1;) { const Loc &t = sv[(size_t)fx].loc[(size_t)fy]; if (t.track == 2) { used = true; break; } const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
+        if (used) continue;
+        std::vector<std::pair<int, int>> ln((size_t)sv[(size_t)rx].loc[(size_t)ry].node_n);
+        int i = (int)ln.size() - 1;
+        for (int fx = rx, fy = ry; fx != -1; --i) { Loc &t = sv[(size_t)fx].loc[(size_t)fy]; if (i >= 0) ln[(size_t)i] = {fx, fy}; t.track = 2; const int nx = t.from_x, ny = t.from_y; fx = nx; fy = ny; }
+        lines.push_back(std::move(ln));
+    }
+    // one alignment per chain (bwt_set_bound :183, bwt_aln_res :200-246)
+    for (const auto &ln : lines) {
+        RescueLine L;
+        const Loc &first = sv[(size_t)ln.front().first].loc[(size_t)ln.front().second], &last = sv[(size_t)ln.back().first].loc[(size_t)ln.back().second];
+        const int pos_first = sv[(size_t)ln.front().first].pos, pos_last = sv[(size_t)ln.back().first].pos;
+        L.ref_id = first.ref_id; L.is_rev = first.is_rev; L.reg_beg = reg_beg; L.reg_len = reg_len;
+        if (first.is_rev) {
+            L.right.read_pos = reg_len + 1 - pos_first; L.left.read_pos = reg_len + 1 - (pos_last + seed_len - 1);
+            L.right.ref_pos = first.ref_pos + seed_len - 1; L.left.ref_pos = last.ref_pos;
+        } else {
+            L.left.read_pos = pos_first; L.right.read_pos = pos_last + seed_len - 1;
+            L.left.ref_pos = first.ref_pos; L.right.ref_pos = last.ref_pos + seed_len - 1;
+        }
+        const int ext = 100;
+        const int after = read_len - (reg_beg + reg_len - 1), before = reg_beg - 1;
+        if (L.is_rev) { L.left_eta = after > ext ? ext : after; L.extra_end = reg_beg + reg_len + L.left_eta - 1; L.right_eta = before > ext ? ext : before; L.extra_beg = reg_beg - L.right_eta; }
+        else { L.left_eta = before > ext ? ext : before; L.extra_beg = reg_beg - L.left_eta; L.right_eta = after > ext ? ext : after; L.extra_end = reg_beg + reg_len + L.right_eta - 1; }
+        const int extra_len = reg_len + L.left_eta + L.right_eta;
+        L.query.resize((size_t)extra_len);
+        for (int i = 0; i < extra_len; ++i) {
+            const uint8_t c = bseq[L.extra_beg - 1 + i];
+            if (L.is_rev) L.query[(size_t)(extra_len - 1 - i)] = c < 4 ? 3 - c : 4; else L.query[(size_t)i] = c;
+        }
+        const int64_t want = L.left.ref_pos - (L.left.read_pos - 1 + L.left_eta) - seed_len;
+        L.ref_start = want < 1 ? 1 : want;
+        L.ref_len = (int)(L.right.ref_pos + reg_len - L.right.read_pos + L.right_eta + seed_len - L.ref_start + 1);
+        if (L.ref_len < 0 || !fetch_ref(ix, L.ref_id + 1, L.ref_start - 1, &L.ref_len, L.target)) continue;      // the reference exits here
+        const int mq = L.right.read_pos - L.left.read_pos + 1, mt = (int)(L.right.ref_pos - L.left.ref_pos + 1);
+        const int64_t t0 = L.left.ref_pos - L.ref_start;
+        if (mq < 0 || mt < 0 || t0 < 0 || t0 + mt > L.ref_len) continue;
+        L.job_mid = jobs.add(L.query.data() + (L.left.read_pos - 1 + L.left_eta), mq, L.target.data() + t0, mt, 0, P.band_w, 0);
+        if (L.left.read_pos > 1 || L.left_eta > 0) {
+            L.left_qlen = L.left.read_pos - 1 + L.left_eta;
+            const int tl = (int)t0;
+            L.lq.resize((size_t)L.left_qlen); L.lt.resize((size_t)tl);
+            for (int i = 0; i < L.left_qlen; ++i) L.lq[(size_t)i] = L.query[(size_t)(L.left_qlen - 1 - i)];
+            for (int i = 0; i < tl; ++i) L.lt[(size_t)i] = L.target[(size_t)(tl - 1 - i)];
+            L.job_left = jobs.add(L.lq.data(), L.left_qlen, L.lt.data(), tl, 1, P.band_w, seed_len * P.match);
+        }
+        if (L.right.read_pos < reg_len || L.right_eta > 0) {
+            L.right_qlen = reg_len - L.right.read_pos + L.right_eta;
+            const int64_t tl = L.ref_start + L.ref_len - 1 - L.right.ref_pos;
+            if (tl < 0 || tl > L.ref_len) continue;         // ksw_extend_core exits on a negative length
+            L.job_right = jobs.add(L.query.data() + L.right.read_pos + L.left_eta, L.right_qlen, L.target.data() + (L.ref_len - tl), (int)tl, 1, P.band_w, seed_len * P.match);
+        }
+        plan.lines.push_back(std::move(L)); plan.region_of.push_back(ri);
+    }
+}
+
+void plan_regions(const ReadResult &R, int read_len, const lamsa_hp_para &P, RescuePlan &plan)
+{
+    plan.lines.clear(); plan.region_of.clear(); plan.regions.clear();
+    std::vector<Reg> regs;
+    collect_regs(R, regs);
+    remain_regs(regs, read_len, P.bwt_seed_len, P.bwt_min_len, P.bwt_max_len, plan.regions);
+}
+}  // namespace
+
+void rescue_plan(const ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const FmIndex &fm, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs)
+{
+    plan_regions(R, read_len, P, plan);
+    for (size_t ri = 0; ri < plan.regions.size(); ++ri) {
+        HostSeeds src{fm, bseq + plan.regions[ri].beg - 1, P.bwt_seed_len, 0};
+        plan_region((int)ri, plan.regions[ri], src, bseq, read_len, ix, P, plan, jobs);
+    }
+}
+
+void rescue_windows(const ReadResult &R, const uint8_t *bseq, int read_len, const lamsa_hp_para &P, RescuePlan &plan, RescueWindows &wins)
+{
+    plan_regions(R, read_len, P, plan);
+    if (wins.win_off.empty()) wins.win_off.push_back(0);
+    plan.first_win = (int64_t)wins.win_off.size() - 1;
+    for (const Reg &reg : plan.regions) {                   // a window per region, also one too short for a seed: it has no k-mers
+        wins.seq.insert(wins.seq.end(), bseq + reg.beg - 1, bseq + reg.end);
+        wins.win_off.push_back((int64_t)wins.seq.size());
+    }
+}
+
+bool rescue_plan_found(const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_fm_out &found, int64_t win_base, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs)
+{
+    for (size_t ri = 0; ri < plan.regions.size(); ++ri) {
+        const Reg &reg = plan.regions[ri];
+        const int64_t w = win_base + plan.first_win + (int64_t)ri, seed_n = reg.end - reg.beg + 1 - P.bwt_seed_len + 1;
+        if (found.kmer_off[w + 1] - found.kmer_off[w] != (seed_n > 0 ? seed_n : 0)) return false;      // not the answers to these windows
+        FoundSeeds src{found, found.kmer_off[w], 0};
+        plan_region((int)ri, reg, src, bseq, read_len, ix, P, plan, jobs);
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------ finish

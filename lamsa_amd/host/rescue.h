@@ -26,6 +26,10 @@ struct FmIndex {
 
 struct RescueBound { int read_pos; int64_t ref_pos; };
 
+// an uncovered read region beg .. end (1-based, inclusive) and the ends of the records next to it (get_remain_reg, src/lamsa_aln.c:583)
+struct RescueAnchor { int is_rev, chr; int64_t pos; };
+struct RescueRegion { int beg, end; std::vector<RescueAnchor> rb, re; };
+
 struct RescueLine {                  // one seed chain that goes to bwt_aln_res (:200-303)
     int ref_id = 0, is_rev = 0, reg_beg = 0, reg_len = 0;
     RescueBound left, right;
@@ -45,10 +49,24 @@ struct RescuePlan {                  // of one read
     std::vector<RescueLine> lines;
     std::vector<int> region_of;      // region index of every line (lines of one region are consecutive)
     std::vector<int> job_base;       // unused by callers; kept for debugging
+    std::vector<RescueRegion> regions;   // the read's uncovered regions, in order
+    int64_t first_win = 0;           // --rescue-gpu: the window of regions[0] in the RescueWindows the read was listed into
 };
+
+// --rescue-gpu: the uncovered regions of many reads as the windows of one lamsa_hp_fm_search (one list per host thread)
+struct RescueWindows { std::vector<uint8_t> seq; std::vector<int64_t> win_off; };
 
 // plan: `bseq` = the read's base codes (0..4).  Jobs are appended to `jobs` (one job list per host thread).
 void rescue_plan(const ReadResult &R, const uint8_t *bseq, int read_len, const Index &ix, const FmIndex &fm, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs);
+
+// The same plan in three steps, the search of all reads of a chunk in one call on the device between the two host steps:
+//   rescue_windows     regions of the read -> plan.regions, one window per region appended to `wins`
+//   lamsa_hp_fm_search (include/lamsa_hp.h) over the windows of the chunk, k = P.bwt_seed_len, max_occ = 5 * 100
+//   rescue_plan_found  seeds -> chains -> jobs from the answers; win_base: where the windows of `wins` begin in the call's window list.
+//                      false: the answers do not belong to these windows
+// Both ways share the code that turns a seed's rows into hits, chains and jobs; the plans and the jobs are the same.
+void rescue_windows(const ReadResult &R, const uint8_t *bseq, int read_len, const lamsa_hp_para &P, RescuePlan &plan, RescueWindows &wins);
+bool rescue_plan_found(const uint8_t *bseq, int read_len, const Index &ix, const lamsa_hp_fm_out &found, int64_t win_base, const lamsa_hp_para &P, RescuePlan &plan, RescueJobs &jobs);
 
 struct DpResults { const int32_t *score, *qle, *tle; const int64_t *cig_off; const int32_t *cigar; int64_t base; };   // base: first job of this thread's list
 

@@ -54,11 +54,57 @@ class HpResult(C.Structure):
                 ("read_len", C.POINTER(C.c_int32)), ("read_status", C.POINTER(C.c_int32)), ("read_tbases", C.POINTER(C.c_int32)), ("read_work", C.POINTER(C.c_int32))]
 
 
+class HpFmIndex(C.Structure):
+    """struct lamsa_hp_fm_index"""
+    _fields_ = [("seq_len", C.c_uint64), ("primary", C.c_uint64), ("L2", C.c_uint64 * 5), ("bwt", C.c_void_p), ("bwt_words", C.c_uint64),
+                ("sa", C.c_void_p), ("n_sa", C.c_uint64), ("sa_intv", C.c_uint64)]
+
+
+class HpFmQueries(C.Structure):
+    """struct lamsa_hp_fm_queries"""
+    _fields_ = [("n_win", C.c_int32), ("seq", C.c_void_p), ("seq_bytes", C.c_int64), ("win_off", C.c_void_p), ("k", C.c_int32), ("max_occ", C.c_int32)]
+
+
+class HpFmOut(C.Structure):
+    """struct lamsa_hp_fm_out"""
+    _fields_ = [("n_kmers", C.c_int64), ("kmer_off", C.POINTER(C.c_int64)), ("lo", C.POINTER(C.c_uint64)), ("hi", C.POINTER(C.c_uint64)),
+                ("pos_off", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_uint64))]
+
+
+def read_fm_index(prefix):
+    """<prefix>.bwt / <prefix>.sa (the reference's index files) as the arrays of lamsa_hp_fm_index: (struct, arrays kept alive)."""
+    hdr = np.fromfile(prefix + ".bwt", np.uint64, 5)
+    bwt = np.fromfile(prefix + ".bwt", np.uint32, offset=40)
+    sh = np.fromfile(prefix + ".sa", np.uint64, 7)
+    if len(hdr) < 5 or len(sh) < 7 or int(sh[0]) != int(hdr[0]) or int(sh[6]) != int(hdr[4]):
+        raise ValueError("%s.sa does not belong to %s.bwt" % (prefix, prefix))
+    sa = np.concatenate([np.array([0xffffffffffffffff], np.uint64), np.fromfile(prefix + ".sa", np.uint64, offset=56)])      # row 0: bwt_restore_sa's -1
+    ix = HpFmIndex()
+    ix.primary = int(hdr[0]); ix.seq_len = int(hdr[4])
+    ix.L2[0] = 0
+    for c in range(4):
+        ix.L2[c + 1] = int(hdr[1 + c])
+    ix.bwt = bwt.ctypes.data; ix.bwt_words = len(bwt); ix.sa = sa.ctypes.data; ix.n_sa = len(sa); ix.sa_intv = int(sh[5])
+    return ix, (bwt, sa)
+
+
+def fm_result(O, n_win):
+    """The arrays of a lamsa_hp_fm_out, copied: (kmer_off, lo, hi, pos_off, pos)."""
+    n = int(O.n_kmers)
+    kmer_off = np.ctypeslib.as_array(O.kmer_off, (n_win + 1,)).copy()
+    lo = np.ctypeslib.as_array(O.lo, (max(n, 1),))[:n].copy(); hi = np.ctypeslib.as_array(O.hi, (max(n, 1),))[:n].copy()
+    pos_off = np.ctypeslib.as_array(O.pos_off, (n + 1,)).copy()
+    tot = int(pos_off[n])
+    pos = np.ctypeslib.as_array(O.pos, (max(tot, 1),))[:tot].copy()
+    return kmer_off, lo, hi, pos_off, pos
+
+
 EXPORTS = ("lamsa_hp_para_init", "lamsa_hp_para_finish", "lamsa_hp_create", "lamsa_hp_destroy",
            "lamsa_hp_last_error", "lamsa_hp_dp_batch", "lamsa_hp_last_kernel_ms", "lamsa_hp_set_scratch_limit",
            "lamsa_hp_align_batch", "lamsa_hp_upload_batch", "lamsa_hp_run_uploaded",
            "lamsa_hp_submit_batch", "lamsa_hp_collect_batch", "lamsa_hp_host_alloc", "lamsa_hp_host_free",
-           "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve", "lamsa_hp_set_result_tags")
+           "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve", "lamsa_hp_set_result_tags",
+           "lamsa_hp_fm_load", "lamsa_hp_fm_search")
 
 TAG_MISMATCHES = 1      # LAMSA_HP_TAG_MISMATCHES: every record of the result stream also lists its mismatches
 TAG_EQX = 2             # LAMSA_HP_TAG_EQX: the CIGARs of the result stream are in =/X form (every M split into '=' 7 and 'X' 8 pieces)
@@ -122,6 +168,10 @@ def load_library(path=None):
         L.lamsa_hp_finish_uploaded.restype = C.c_int
         L.lamsa_hp_set_result_tags.argtypes = [C.c_void_p, C.c_int]
         L.lamsa_hp_set_result_tags.restype = C.c_int
+        L.lamsa_hp_fm_load.argtypes = [C.c_void_p, C.POINTER(HpFmIndex)]
+        L.lamsa_hp_fm_load.restype = C.c_int
+        L.lamsa_hp_fm_search.argtypes = [C.c_void_p, C.POINTER(HpFmQueries), C.POINTER(HpFmOut)]
+        L.lamsa_hp_fm_search.restype = C.c_int
         _lib = L
     return _lib
 
@@ -227,6 +277,27 @@ class LamsaHp:
         cg = np.ctypeslib.as_array(O.cigar, (max(tot, 1),)).copy()
         cigars = [cg[off[i]:off[i + 1]].tolist() for i in range(n)]
         return dict(score=score, qle=qle, tle=tle, status=st, cigars=cigars)
+
+    # ---- the resident FM index
+    def fm_load(self, prefix):
+        """Copy the FM index <prefix>.bwt / <prefix>.sa to the device (replaces an index loaded earlier)."""
+        ix, keep = read_fm_index(prefix)
+        rc = self.L.lamsa_hp_fm_load(self._h, C.byref(ix))
+        if rc != 0:
+            raise RuntimeError("lamsa_hp_fm_load: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
+
+    def fm_search(self, seq, win_off, k, max_occ):
+        """All overlapping k-mers of the windows seq[win_off[w] : win_off[w + 1]] (base codes 0..4) in the loaded index: returns
+        (kmer_off, lo, hi, pos_off, pos) as include/lamsa_hp.h defines them -- inclusive row intervals, (1, 0) when empty, and the
+        suffix-array values in row order of every k-mer with 1 .. max_occ occurrences."""
+        seq = np.ascontiguousarray(seq, np.uint8); win_off = np.ascontiguousarray(win_off, np.int64)
+        n_win = max(len(win_off) - 1, 0)
+        Q = HpFmQueries(n_win, seq.ctypes.data, len(seq), win_off.ctypes.data, int(k), int(max_occ))
+        O = HpFmOut()
+        rc = self.L.lamsa_hp_fm_search(self._h, C.byref(Q), C.byref(O))
+        if rc != 0:
+            raise RuntimeError("lamsa_hp_fm_search: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
+        return fm_result(O, n_win)
 
     # ---- the hot path proper
     def _batch_struct(self, batch):
