@@ -9,6 +9,8 @@
  * second round (2')/(3') run on the GPU behind lamsa_hp_align_batch(); seeding,
  * FASTA/FASTQ + GEM-map parsing, the BWT rescue (stage 4), result ranking and SAM
  * output stay with the host caller, exactly as SURVEY.md section 8(b) draws the line.
+ * Two calls move work of the host side onto an FM index resident in HBM: lamsa_hp_fm_search (the exact search of stage 4) and
+ * lamsa_hp_fm_seed (seeding itself, exact seeds, straight into the hit records of a lamsa_hp_batch; no mapper, no map text).
  *
  * Plain pointers and sizes only; every buffer handed in is caller-owned host memory,
  * every buffer handed out is callee-owned and valid until the next call on the same
@@ -305,6 +307,49 @@ typedef struct lamsa_hp_fm_queries { int32_t n_win; const uint8_t *seq; int64_t 
 typedef struct lamsa_hp_fm_out { int64_t n_kmers; const int64_t *kmer_off; /* [n_win+1] */ const uint64_t *lo, *hi; /* [n_kmers] */
                                  const int64_t *pos_off; /* [n_kmers+1] */ const uint64_t *pos; } lamsa_hp_fm_out;
 int lamsa_hp_fm_search(lamsa_hp_handle *h, const lamsa_hp_fm_queries *q, lamsa_hp_fm_out *out);
+
+/* ------------------------------------------------------------------------------------
+ * Seeding in the resident index: the seeds of a batch of reads are cut, searched exactly and located on the device, and come back as
+ * the hit records of a lamsa_hp_batch -- what split_seed (src/lamsa_aln.c:252), the GEM mapper and gem_map_msg (src/gem_parse.c) make
+ * together, for exact hits only.  No mapper, no seed file, no map text.  The definition:
+ *   Inputs: the reads (read_off / read_seq as in lamsa_hp_batch, codes 0..4); seed_len (1..63), seed_step (>= 1), max_hits (1..16383);
+ *   the contig table (n_seqs, seq_offset, seq_len as in lamsa_hp_ref); the index loaded on the handle, whose text is the forward
+ *   reference followed by its reverse complement, seq_len = 2 * l_pac.
+ *   Per read of length L:  seed_all = L < seed_len ? 0 : 1 + (L - seed_len) / seed_step;
+ *                          last_len = L - seed_len - (seed_all - 1) * seed_step  (what lamsa_hp_align_batch checks);
+ *   seed i (1-based) is read[(i-1) * seed_step .. + seed_len).  Let n be the number of rows of the seed's interval
+ *   (bwt_match_exact_alt from the whole index); n = 0 when a base code is above 3.
+ *     n = 0:          the seed gets no slot.
+ *     n > max_hits:   the seed keeps its slot (seed_id = i) with no hits, as gem_map_msg does for a line with more than per_aln_m hits
+ *                     (src/gem_parse.c:243-246).
+ *     otherwise, for the rows in ascending row order: p = the row's text position (bwt_sa); is_rev = p >= l_pac;
+ *                     f = is_rev ? 2 * l_pac - 1 - p : p;  c = the contig that holds f (bns_pos2rid);
+ *                     pos = f - seq_offset[c] + 1 - (is_rev ? seed_len - 1 : 0);
+ *                     the row is kept iff pos >= 1 and pos + seed_len - 1 <= seq_len[c]  (an occurrence across a contig boundary, across
+ *                     the middle of the doubled text, or -- on '-' -- beginning in the contig before, is none);
+ *                     a kept row is the hit h_pos = pos, h_chr = c + 1, h_strand = is_rev ? -1 : +1, h_nm = 0, h_len_dif = 0,
+ *                     CIGAR "seed_len M".  If no row is kept, the seed gets no slot.
+ *   Hits of a slot stay in row order, slots in seed order, reads in input order.
+ * Where the FASTA had N the .pac holds substituted bases, and a seed may hit there; filtering by <ref>.amb is the caller's.
+ * `out` is a complete lamsa_hp_batch in the compact form: h_cig_off = NULL, cig = NULL, cig8 one byte per hit, n_cig = the number of
+ * hits.  read_off / read_seq are the caller's arrays; everything else is callee-owned and valid until the next lamsa_hp_fm_seed on the
+ * handle.  Every pointer is non-null, also for zero reads or zero hits.  It can be handed to lamsa_hp_align_batch /
+ * lamsa_hp_submit_batch of any handle created with seed_len, seed_step and that reference.
+ * LAMSA_HP_EINVAL: no index loaded; seed_len outside 1..63, seed_step < 1, max_hits outside 1..16383; offsets that do not start at 0 or
+ * that decrease; a read longer than 2^24; a base code above 4; a contig table that is empty, not contiguous, or whose end is not the
+ * index's seq_len / 2 (the index of another genome).  LAMSA_HP_ENOMEM as elsewhere; the handle stays usable after every error.
+ * The call blocks and shares its device buffers with lamsa_hp_fm_search.  Rows are located LAMSA_HP_FM_SLICE (default 2^22) at a time
+ * and a slice's hits fetched before the next is located, so the device buffers are bounded by the slice and by the number of seeds; the
+ * hits travel once, 13 bytes each (position, contig, strand); what is the same for every exact hit is filled in on the host.
+ * Exact seeds suit accurate reads: a 50-mer survives 1 % error with probability 0.61, 5 % with 0.08.
+ * lamsa_hp_last_kernel_ms 21 / 22 / 23 after this call: search + scan of the row counts, locate + compaction of all slices, slots + emit.
+ * ---------------------------------------------------------------------------------- */
+typedef struct lamsa_hp_seed_queries {
+    int32_t n_reads; const int64_t *read_off; const uint8_t *read_seq;
+    int32_t seed_len, seed_step, max_hits;
+    int32_t n_seqs; const int64_t *seq_offset; const int32_t *seq_len;
+} lamsa_hp_seed_queries;
+int lamsa_hp_fm_seed(lamsa_hp_handle *h, const lamsa_hp_seed_queries *q, lamsa_hp_batch *out);
 
 #ifdef __cplusplus
 }

@@ -433,3 +433,184 @@ extern "C" int lamsa_hp_fm_search(lamsa_hp_handle *h, const lamsa_hp_fm_queries 
     }
     return LAMSA_HP_OK;
 }
+
+// ------------------------------------------------------------------ seeding in the resident index: lamsa_hp_fm_seed
+#include "hp_seed.h"
+
+// The same plain grids as the two FM kernels: one seed / one located row per lane, chains of dependent 64-byte block reads, no LDS.
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_seed_search(SeedArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t j = (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; j < a.n_seeds; j += step) seed_search_lane(a, j);
+}
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_seed_locate(SeedArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t t = a.t0 + (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; t < a.t1; t += step) seed_locate_lane(a, t);
+}
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_seed_hits(SeedArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t t = a.t0 + (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; t < a.t1; t += step) seed_hits_lane(a, t);
+}
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_seed_slot(SeedArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK;
+    for (int64_t j = (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; j < a.n_seeds; j += step) seed_slot_lane(a, j);
+}
+__global__ __launch_bounds__(FM_BLOCK, 8) void k_seed_emit(SeedArgs a)
+{
+    const int64_t step = (int64_t)gridDim.x * FM_BLOCK, n = a.n_seeds + a.n_reads + 1;
+    for (int64_t x = (int64_t)blockIdx.x * FM_BLOCK + threadIdx.x; x < n; x += step) seed_emit_lane(a, x);
+}
+
+extern "C" int lamsa_hp_fm_seed(lamsa_hp_handle *h, const lamsa_hp_seed_queries *q, lamsa_hp_batch *out)
+{
+    if (!h || !q || !out) return LAMSA_HP_EINVAL;
+    if (!h->fm_bwt) { h->err = "fm seed: no index loaded"; return LAMSA_HP_EINVAL; }
+    if (q->seed_len < 1 || q->seed_len > 63 || q->seed_step < 1 || q->max_hits < 1 || q->max_hits > HP_SEED_MAX_HITS) { h->err = "fm seed: seed_len outside 1..63, seed_step < 1 or max_hits outside 1..16383"; return LAMSA_HP_EINVAL; }
+    const int n = q->n_reads, nc = q->n_seqs;
+    if (n < 0 || (n > 0 && (!q->read_off || !q->read_seq))) { h->err = "fm seed: negative n_reads or a null array"; return LAMSA_HP_EINVAL; }
+    // the contig table must be the one of the loaded index: contiguous from 0 to half the doubled text
+    if (nc < 1 || !q->seq_offset || !q->seq_len || q->seq_offset[0] != 0) { h->err = "fm seed: empty contig table, or one that does not start at 0"; return LAMSA_HP_EINVAL; }
+    for (int c = 0; c < nc; ++c)
+        if (q->seq_len[c] < 0 || (c + 1 < nc && q->seq_offset[c + 1] != q->seq_offset[c] + q->seq_len[c])) { h->err = "fm seed: the contigs do not lie back to back"; return LAMSA_HP_EINVAL; }
+    const int64_t l_pac = q->seq_offset[nc - 1] + q->seq_len[nc - 1];
+    if ((h->fm_ix.seq_len & 1) || (uint64_t)l_pac != h->fm_ix.seq_len / 2) { h->err = "fm seed: the contig table does not end where the index's forward text ends (the index of another genome?)"; return LAMSA_HP_EINVAL; }
+    if (n > 0 && q->read_off[0] != 0) { h->err = "fm seed: offsets must start at 0"; return LAMSA_HP_EINVAL; }
+    const int64_t sl = q->seed_len, ss = q->seed_step;
+    h->sd_all.assign((size_t)n + 1, 0); h->sd_last.assign((size_t)n + 1, 0); h->sd_off.assign((size_t)n + 1, 0); h->sd_seed_off.assign((size_t)n + 1, 0);
+    for (int r = 0; r < n; ++r) {
+        const int64_t L = q->read_off[r + 1] - q->read_off[r];
+        if (L < 0) { h->err = "fm seed: read offsets decrease"; return LAMSA_HP_EINVAL; }
+        if (L > (1 << 24)) { h->err = "fm seed: read longer than 2^24 bases"; return LAMSA_HP_EINVAL; }
+        const int64_t sa = L < sl ? 0 : 1 + (L - sl) / ss;
+        h->sd_all[(size_t)r] = (int32_t)sa; h->sd_last[(size_t)r] = (int32_t)(L - sl - (sa - 1) * ss);
+        h->sd_off[(size_t)r + 1] = h->sd_off[(size_t)r] + sa;
+    }
+    const int64_t n_bases = n ? q->read_off[n] : 0, N = h->sd_off[(size_t)n];
+    { unsigned bad = 0; for (int64_t i = 0; i < n_bases; ++i) bad |= q->read_seq[i] > 4; if (bad) { h->err = "fm seed: read base code > 4"; return LAMSA_HP_EINVAL; } }
+    HIPCHK(h, hipSetDevice(h->device), LAMSA_HP_ENODEV);
+    h->sd_seed_id.assign(1, 0); h->sd_hit_off.assign(1, 0); h->sd_pos.assign(1, 0); h->sd_chr.assign(1, 0); h->sd_strand.assign(1, 0);
+    h->sd_nm.assign(1, 0); h->sd_len_dif.assign(1, 0); h->sd_cig_n.assign(1, 0); h->sd_cig8.assign(1, 0);
+    h->kernel_ms[21] = h->kernel_ms[22] = h->kernel_ms[23] = 0;
+    static const int64_t zero64 = 0; static const uint8_t zero8 = 0;
+    int64_t n_slots = 0, n_hits = 0;
+    auto hand_out = [&]() {
+        out->n_reads = n; out->read_off = q->read_off ? q->read_off : &zero64; out->read_seq = q->read_seq ? q->read_seq : &zero8;
+        out->seed_all = h->sd_all.data(); out->last_len = h->sd_last.data(); out->seed_off = h->sd_seed_off.data(); out->seed_id = h->sd_seed_id.data(); out->hit_off = h->sd_hit_off.data();
+        out->h_pos = h->sd_pos.data(); out->h_chr = h->sd_chr.data(); out->h_strand = h->sd_strand.data(); out->h_nm = h->sd_nm.data(); out->h_len_dif = h->sd_len_dif.data();
+        out->h_cig_off = nullptr; out->h_cig_n = h->sd_cig_n.data(); out->cig = nullptr; out->n_cig = n_hits; out->cig8 = h->sd_cig8.data();
+    };
+    hand_out();
+    if (N == 0) return LAMSA_HP_OK;
+
+    const int64_t slice = getenv("LAMSA_HP_FM_SLICE") ? std::max<int64_t>(1, atoll(getenv("LAMSA_HP_FM_SLICE"))) : ((int64_t)4 << 20);      // rows located per pass (tests lower it)
+    const size_t nN = (size_t)N, nT = (size_t)((N + HP_FM_TILE - 1) / HP_FM_TILE);
+    const size_t i_off = al256((size_t)n_bases + 16), i_sd = i_off + al256(8 * ((size_t)n + 1)), i_co = i_sd + al256(8 * ((size_t)n + 1)), i_cl = i_co + al256(8 * (size_t)nc), in_bytes = i_cl + al256(4 * (size_t)nc);
+    const size_t o_cnt = al256(8 * nN), o_over = o_cnt + al256(4 * nN), o_kept = o_over + al256(4 * nN), o_slot = o_kept + al256(4 * nN), o_roff = o_slot + al256(4 * nN),
+                 o_soff = o_roff + al256(8 * (nN + 1)), o_koff = o_soff + al256(8 * (nN + 1)), o_sid = o_koff + al256(8 * (nN + 1)), o_hoff = o_sid + al256(4 * nN),
+                 o_sdo = o_hoff + al256(8 * (nN + 1)), o_tsum = o_sdo + al256(8 * ((size_t)n + 1)), o_toff = o_tsum + al256(4 * nT), out_bytes = o_toff + al256(8 * (nT + 1));
+    if (h->fm_in.ensure(in_bytes)) { (void)hipGetLastError(); h->err = "hipMalloc(fm seed in)"; return LAMSA_HP_ENOMEM; }
+    if (h->fm_out.ensure(out_bytes)) { (void)hipGetLastError(); h->err = "hipMalloc(fm seed out)"; return LAMSA_HP_ENOMEM; }
+    char *din = (char *)h->fm_in.p, *dout = (char *)h->fm_out.p;
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(din, q->read_seq, (size_t)n_bases, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + i_off, q->read_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + i_sd, h->sd_off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + i_co, q->seq_offset, 8 * (size_t)nc, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(din + i_cl, q->seq_len, 4 * (size_t)nc, hipMemcpyHostToDevice, s), LAMSA_HP_EKERNEL);
+
+    SeedArgs a; memset(&a, 0, sizeof a);
+    a.ix.seq_len = h->fm_ix.seq_len; a.ix.primary = h->fm_ix.primary; for (int c = 0; c < 5; ++c) a.ix.L2[c] = h->fm_ix.L2[c];
+    a.ix.bwt = (const uint32_t *)h->fm_bwt; a.ix.sa = (const uint64_t *)h->fm_sa; a.ix.sa_intv = h->fm_ix.sa_intv;
+    a.read_seq = (const uint8_t *)din; a.read_off = (const int64_t *)(din + i_off); a.sd_off = (const int64_t *)(din + i_sd);
+    a.n_reads = n; a.seed_len = q->seed_len; a.seed_step = q->seed_step; a.max_hits = q->max_hits; a.n_seeds = N;
+    a.seq_offset = (const int64_t *)(din + i_co); a.seq_len = (const int32_t *)(din + i_cl); a.n_seqs = nc; a.l_pac = l_pac;
+    a.lo = (uint64_t *)dout; a.cnt = (int32_t *)(dout + o_cnt); a.over = (int32_t *)(dout + o_over); a.kept = (int32_t *)(dout + o_kept); a.slot = (int32_t *)(dout + o_slot);
+    a.row_off = (const int64_t *)(dout + o_roff); a.slot_off = (const int64_t *)(dout + o_soff); a.kept_off = (const int64_t *)(dout + o_koff);
+    a.seed_id = (int32_t *)(dout + o_sid); a.hit_off = (int64_t *)(dout + o_hoff); a.seed_off = (int64_t *)(dout + o_sdo);
+    auto grid_of = [](int64_t items) { const int64_t g = (items + FM_BLOCK - 1) / FM_BLOCK; return dim3((unsigned)(g < FM_MAX_GRID ? g : FM_MAX_GRID)); };
+    auto scan = [&](const int32_t *cnt, int64_t items, const int64_t *off, char *tiles) {       // exclusive scan of cnt[items] -> off[items + 1]; tiles: the tile sums, then their offsets
+        FmScanArgs sc;
+        sc.cnt = cnt; sc.n = items; sc.n_tiles = (items + HP_FM_TILE - 1) / HP_FM_TILE; sc.pos_off = (int64_t *)off;
+        sc.tile_sum = (int32_t *)tiles; sc.tile_off = (int64_t *)(tiles + al256(4 * (size_t)sc.n_tiles));
+        const dim3 sgrid((unsigned)(sc.n_tiles < 8 * FM_MAX_GRID ? sc.n_tiles : 8 * FM_MAX_GRID));
+        hipLaunchKernelGGL(k_fm_scan_sums, sgrid, dim3(64), 0, s, sc);
+        hipLaunchKernelGGL(k_fm_scan_tiles, dim3(1), dim3(64), 0, s, sc);
+        hipLaunchKernelGGL(k_fm_scan_write, sgrid, dim3(64), 0, s, sc);
+    };
+    float ms = 0;
+    // ---- seeds -> row intervals -> the flat row list
+    int64_t total = 0;
+    HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+    hipLaunchKernelGGL(k_seed_search, grid_of(N), dim3(FM_BLOCK), 0, s, a);
+    scan(a.cnt, N, a.row_off, dout + o_tsum);
+    HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(&total, a.row_off + N, 8, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    hipEventElapsedTime(&h->kernel_ms[21], h->ev0, h->ev1);
+    if (total < 0 || total > N * (int64_t)q->max_hits) { h->err = "fm seed: the device scan went wrong"; return LAMSA_HP_EKERNEL; }
+
+    // ---- rows -> hits, a slice of the flat row list at a time: the device buffers stay bounded whatever n_seeds * max_hits is, and the hits of
+    // a slice, compacted in flat row order, are the next hits of the batch
+    const size_t m_max = (size_t)std::min(slice, total), mT = (m_max + HP_FM_TILE - 1) / HP_FM_TILE;
+    const size_t p_pos = al256(8 * m_max), p_chr = 2 * p_pos, p_keep = p_chr + al256(4 * m_max), p_koff = p_keep + al256(4 * m_max), p_spos = p_koff + al256(8 * (m_max + 1)),
+                 p_schr = p_spos + al256(8 * m_max), p_sstr = p_schr + al256(4 * m_max), p_tiles = p_sstr + al256(m_max), pos_bytes = p_tiles + al256(4 * mT) + al256(8 * (mT + 1));
+    if (total > 0 && h->fm_pos.ensure(pos_bytes)) { (void)hipGetLastError(); h->err = "hipMalloc(fm seed rows)"; return LAMSA_HP_ENOMEM; }
+    char *dp = (char *)h->fm_pos.p;
+    a.p_seed = (int64_t *)dp; a.p_pos = (int64_t *)(dp + p_pos); a.p_chr = (int32_t *)(dp + p_chr); a.keep = (int32_t *)(dp + p_keep); a.keep_off = (const int64_t *)(dp + p_koff);
+    a.s_pos = (int64_t *)(dp + p_spos); a.s_chr = (int32_t *)(dp + p_schr); a.s_strand = (int8_t *)(dp + p_sstr);
+    h->sd_pos.clear(); h->sd_chr.clear(); h->sd_strand.clear();
+    h->sd_pos.reserve((size_t)total + 1); h->sd_chr.reserve((size_t)total + 1); h->sd_strand.reserve((size_t)total + 1);
+    for (int64_t t0 = 0; t0 < total; t0 += slice) {
+        a.t0 = t0; a.t1 = std::min(total, t0 + slice);
+        const int64_t m = a.t1 - a.t0;
+        int64_t got = 0;
+        HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+        hipLaunchKernelGGL(k_seed_locate, grid_of(m), dim3(FM_BLOCK), 0, s, a);
+        scan(a.keep, m, a.keep_off, dp + p_tiles);
+        hipLaunchKernelGGL(k_seed_hits, grid_of(m), dim3(FM_BLOCK), 0, s, a);
+        HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipMemcpyAsync(&got, a.keep_off + m, 8, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+        hipEventElapsedTime(&ms, h->ev0, h->ev1); h->kernel_ms[22] += ms;
+        if (got < 0 || got > m) { h->err = "fm seed: the device scan went wrong"; return LAMSA_HP_EKERNEL; }
+        if (got == 0) continue;
+        const size_t at = (size_t)n_hits;
+        n_hits += got;
+        h->sd_pos.resize((size_t)n_hits); h->sd_chr.resize((size_t)n_hits); h->sd_strand.resize((size_t)n_hits);
+        HIPCHK(h, hipMemcpyAsync(h->sd_pos.data() + at, a.s_pos, 8 * (size_t)got, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipMemcpyAsync(h->sd_chr.data() + at, a.s_chr, 4 * (size_t)got, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipMemcpyAsync(h->sd_strand.data() + at, a.s_strand, (size_t)got, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+        HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    }
+
+    // ---- slots: a seed with a kept row, or with more rows than max_hits; then every slot's seed id and first hit, every read's first slot
+    int64_t ends[2] = {0, 0};
+    HIPCHK(h, hipEventRecord(h->ev0, s), LAMSA_HP_EKERNEL);
+    hipLaunchKernelGGL(k_seed_slot, grid_of(N), dim3(FM_BLOCK), 0, s, a);
+    scan(a.slot, N, a.slot_off, dout + o_tsum);
+    scan(a.kept, N, a.kept_off, dout + o_tsum);
+    hipLaunchKernelGGL(k_seed_emit, grid_of(N + n + 1), dim3(FM_BLOCK), 0, s, a);
+    HIPCHK(h, hipGetLastError(), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipEventRecord(h->ev1, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(&ends[0], a.slot_off + N, 8, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(&ends[1], a.kept_off + N, 8, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(h->sd_seed_off.data(), a.seed_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    hipEventElapsedTime(&h->kernel_ms[23], h->ev0, h->ev1);
+    n_slots = ends[0];
+    if (n_slots < 0 || n_slots > N || ends[1] != n_hits) { h->err = "fm seed: the slices' hits and the seeds' counts do not add up"; return LAMSA_HP_EKERNEL; }
+    h->sd_seed_id.assign((size_t)n_slots + 1, 0); h->sd_hit_off.assign((size_t)n_slots + 1, 0);
+    if (n_slots > 0) HIPCHK(h, hipMemcpyAsync(h->sd_seed_id.data(), a.seed_id, 4 * (size_t)n_slots, hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipMemcpyAsync(h->sd_hit_off.data(), a.hit_off, 8 * ((size_t)n_slots + 1), hipMemcpyDeviceToHost, s), LAMSA_HP_EKERNEL);
+    HIPCHK(h, hipStreamSynchronize(s), LAMSA_HP_EKERNEL);
+    // what is the same for every exact hit never crosses the bus: NM 0, no length difference, one CIGAR element "seed_len M"
+    h->sd_pos.resize((size_t)n_hits + 1); h->sd_chr.resize((size_t)n_hits + 1); h->sd_strand.resize((size_t)n_hits + 1);
+    h->sd_nm.assign((size_t)n_hits + 1, 0); h->sd_len_dif.assign((size_t)n_hits + 1, 0); h->sd_cig_n.assign((size_t)n_hits + 1, 1); h->sd_cig8.assign((size_t)n_hits + 1, (uint8_t)q->seed_len);
+    hand_out();
+    return LAMSA_HP_OK;
+}

@@ -44,6 +44,9 @@ struct lamsa_hp_handle {
     void *fm_bwt = nullptr, *fm_sa = nullptr; lamsa_hp_fm_index fm_ix = {};      // fm_ix: sizes and counts (its pointers are not kept); fm_bwt == nullptr: no index
     DevBuf fm_in, fm_out, fm_pos;
     std::vector<int64_t> fm_kmer_off, fm_pos_off; std::vector<uint64_t> fm_lo, fm_hi, fm_posv;
+    // lamsa_hp_fm_seed: its callee-owned batch (the device buffers are the search's: both calls block)
+    std::vector<int32_t> sd_all, sd_last, sd_seed_id, sd_chr; std::vector<int64_t> sd_off, sd_seed_off, sd_hit_off, sd_pos;
+    std::vector<int8_t> sd_strand; std::vector<int16_t> sd_nm, sd_len_dif; std::vector<uint8_t> sd_cig_n, sd_cig8;
     std::string err;
 };
 

@@ -18,6 +18,8 @@
 // likewise the resident FM index: without the two calls --rescue-gpu says so and stage 4 searches on the host as it does by default
 #pragma weak lamsa_hp_fm_load
 #pragma weak lamsa_hp_fm_search
+// and seeding in that index: without lamsa_hp_fm_seed --seed-fm is an error (there is no host seeding path)
+#pragma weak lamsa_hp_fm_seed
 #include <algorithm>
 #include <atomic>
 #include <cctype>
@@ -1161,6 +1163,16 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     if (!load_index(opt.ref_prefix, ix, err)) { fprintf(stderr, "[lamsa_aln] %s\n", err.c_str()); return 1; }
     const std::string map_path = opt.seed_result.empty() ? opt.reads + ".seed.gem.map" : opt.seed_result;
     const bool from_hits = !opt.hits.empty();
+    // --seed-fm: the hit records of every chunk come from lamsa_hp_fm_seed (include/lamsa_hp.h): no mapper, no .gem index, no seed files,
+    // no map text.  It needs the reference's FM index files and a library that has the call; there is no host seeding path.
+    const bool seed_fm = opt.seed_fm != 0;
+    FmIndex fm; bool fm_loaded = false;
+    if (seed_fm) {
+        if (lamsa_hp_fm_load == nullptr || lamsa_hp_fm_seed == nullptr) { fprintf(stderr, "[lamsa_aln] --seed-fm: this library has no lamsa_hp_fm_load / lamsa_hp_fm_seed\n"); return 2; }
+        std::string e2;
+        if (!fm.load(opt.ref_prefix, e2)) { fprintf(stderr, "[lamsa_aln] --seed-fm needs %s.bwt and %s.sa (lamsa index): %s\n", opt.ref_prefix.c_str(), opt.ref_prefix.c_str(), e2.c_str()); return 2; }
+        fm_loaded = true;
+    }
     if (from_hits) {
         HitsHeader hh;
         if (!hitsf.open(opt.hits) || hitsf.n < sizeof hh) { fprintf(stderr, "[lamsa_aln] Can't open hit stream %s\n", opt.hits.c_str()); return 1; }
@@ -1169,6 +1181,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             fprintf(stderr, "[lamsa_aln] %s is not a hit stream written with these seeding options (-T, -l, -i, -p)\n", opt.hits.c_str()); return 1;
         }
         hitsf.pos = sizeof hh;
+    } else if (seed_fm) {                               // (no seed result to open)
     } else if (opt.mapper_pid) { mapt.open_follow(map_path, opt.mapper_pid);
     } else if (!mapt.open(map_path)) { fprintf(stderr, "[lamsa_aln] Can't open seed-result file %s (seeding is not run by this build: provide the GEM map, as with the reference's -N)\n", map_path.c_str()); return 1; }
     FastxReader fx;
@@ -1198,7 +1211,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
         } else if (fx.mapped()) {
             const size_t S = fx.size(), lo = S / (size_t)sn * (size_t)si, hi = si + 1 == sn ? S : S / (size_t)sn * (size_t)(si + 1);
             fx.restrict(lo, hi);
-            if (si > 0) {
+            if (si > 0 && !seed_fm) {
                 FastxReader probe; Read first;
                 if (probe.open(opt.reads)) probe.restrict(lo, hi);
                 // the first read of the part that has seeds at all (a read shorter than a seed has no line in the map)
@@ -1247,7 +1260,7 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             const long r0 = total * si / sn, r1 = total * (si + 1) / sn;
             Read d; const char *la, *lb;
             for (long k = 0; k < r0; ++k) {
-                if (!fx.next(d) || !mapt.take(seeds_of(P, (int)d.seq.size()), la, lb)) { fprintf(stderr, "[lamsa_read_seq] seeds' GEM map result does not match the reads\n"); return 1; }
+                if (!fx.next(d) || (!seed_fm && !mapt.take(seeds_of(P, (int)d.seq.size()), la, lb))) { fprintf(stderr, "[lamsa_read_seq] seeds' GEM map result does not match the reads\n"); return 1; }
             }
             reads_left = r1 - r0;
         }
@@ -1279,22 +1292,41 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
         if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_set_result_tags failed: %d %s\n", e, lamsa_hp_last_error(hh)); for (lamsa_hp_handle *x : hs) lamsa_hp_destroy(x); return 2; }
     }
     // stage (4): needs the reference's FM index files and a second handle for its DP batches (a handle is single-threaded)
-    FmIndex fm; lamsa_hp_handle *h_dp = nullptr; bool rescue = false; long n_rescue_jobs = 0, n_rescue_kmers = 0;
+    lamsa_hp_handle *h_dp = nullptr; bool rescue = false; long n_rescue_jobs = 0, n_rescue_kmers = 0;
     if (P.bwt_max_len > 0 && !opt.parse_only) {
         std::string e2;
-        if (!fm.load(opt.ref_prefix, e2)) fprintf(stderr, "[lamsa_aln] note: stage 4 (BWT rescue of uncovered regions <= -R %d bp) is skipped: %s; output equals the reference's with -R 0\n", P.bwt_max_len, e2.c_str());
+        if (!fm_loaded && !fm.load(opt.ref_prefix, e2)) fprintf(stderr, "[lamsa_aln] note: stage 4 (BWT rescue of uncovered regions <= -R %d bp) is skipped: %s; output equals the reference's with -R 0\n", P.bwt_max_len, e2.c_str());
         else if (lamsa_hp_create(&h_dp, &P, nullptr, devs[0]) != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] cannot create the stage-4 handle\n"); for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh); return 2; }
         else rescue = true;
     }
     // --rescue-gpu: the index goes into the stage-4 handle once; every chunk's windows are then searched there in one call
+    lamsa_hp_fm_index fmx; memset(&fmx, 0, sizeof fmx);
+    if (fm_loaded || rescue) {
+        fmx.seq_len = fm.seq_len; fmx.primary = fm.primary; for (int c = 0; c < 5; ++c) fmx.L2[c] = fm.L2[c];
+        fmx.bwt = fm.bwt.data(); fmx.bwt_words = (uint64_t)fm.bwt.size() - 4; fmx.sa = fm.sa.data(); fmx.n_sa = fm.n_sa; fmx.sa_intv = fm.sa_intv;      // (FmIndex::load keeps 4 spare words)
+    }
+    // --seed-fm: a handle of its own per device for the seeding calls, the index loaded into it once: a handle is single-threaded, and a chunk
+    // is seeded beside the kernels and beside stage 4 of earlier chunks.  With --rescue-gpu too, stage 4 searches in the seeding handle of its
+    // device, one call at a time (fm_m), so that the device holds the index once.
+    std::map<int, lamsa_hp_handle *> seed_h; std::mutex fm_m; long n_seeded = 0; double seed_s = 0, seed_kernel_ms = 0;
+    auto destroy_seed_handles = [&]() { for (auto &kv : seed_h) lamsa_hp_destroy(kv.second); seed_h.clear(); };
+    for (size_t g = 0; seed_fm && g < devs.size(); ++g) {
+        if (seed_h.count(devs[g])) continue;
+        lamsa_hp_handle *hh = nullptr;
+        int e = lamsa_hp_create(&hh, &P, nullptr, devs[g]);
+        if (e == LAMSA_HP_OK) { seed_h[devs[g]] = hh; e = lamsa_hp_fm_load(hh, &fmx); }
+        if (e != LAMSA_HP_OK) {
+            fprintf(stderr, "[lamsa_aln] --seed-fm: cannot put the FM index on device %d: %d %s\n", devs[g], e, hh ? lamsa_hp_last_error(hh) : "no usable MI355X / HIP device");
+            destroy_seed_handles(); if (h_dp) lamsa_hp_destroy(h_dp); for (lamsa_hp_handle *x : hs) lamsa_hp_destroy(x); return 2;
+        }
+    }
+    lamsa_hp_handle *h_fm = h_dp;                          // where stage 4 searches
     bool rescue_gpu = false;
     if (rescue && opt.rescue_gpu) {
         if (lamsa_hp_fm_load == nullptr || lamsa_hp_fm_search == nullptr) fprintf(stderr, "[lamsa_aln] note: --rescue-gpu: this library has no lamsa_hp_fm_load / lamsa_hp_fm_search; stage 4 searches on the host\n");
+        else if (seed_fm) { h_fm = seed_h[devs[0]]; rescue_gpu = true; }
         else {
-            lamsa_hp_fm_index fx; memset(&fx, 0, sizeof fx);
-            fx.seq_len = fm.seq_len; fx.primary = fm.primary; for (int c = 0; c < 5; ++c) fx.L2[c] = fm.L2[c];
-            fx.bwt = fm.bwt.data(); fx.bwt_words = (uint64_t)fm.bwt.size() - 4; fx.sa = fm.sa.data(); fx.n_sa = fm.n_sa; fx.sa_intv = fm.sa_intv;      // (FmIndex::load keeps 4 spare words)
-            const int e = lamsa_hp_fm_load(h_dp, &fx);
+            const int e = lamsa_hp_fm_load(h_dp, &fmx);
             if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_load failed: %d %s\n", e, lamsa_hp_last_error(h_dp)); lamsa_hp_destroy(h_dp); for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh); return 2; }
             rescue_gpu = true;
         }
@@ -1382,9 +1414,10 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 }
                 break;
             }
-            const char *la, *lb;
+            const char *la = nullptr, *lb = nullptr;
             bool got;
-            if (mapt.following()) {
+            if (seed_fm) got = true;                         // no map lines: prepare() seeds the chunk on the GPU
+            else if (mapt.following()) {
                 if (c->text.capacity() < (size_t)opt.chunk_reads + 1) c->text.reserve((size_t)opt.chunk_reads + 1);      // no reallocation: the spans point into the strings
                 c->text.emplace_back();
                 got = mapt.take_follow(seeds_of(P, (int)rd.seq.size()), c->text.back());
@@ -1435,6 +1468,39 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
                 for (int b : bad) if (b) { fprintf(stderr, "[lamsa_read_seq] the hit stream does not match the reads\n"); c->ret = 1; break; }
             }
             parse_s += now_s() - t0; return c;
+        }
+        if (seed_fm) {
+            // reads -> base codes on all threads, then one lamsa_hp_fm_seed on the seeding handle of the device the chunk will go to; its batch
+            // is the handle's until the next seeding call, so it is copied into the chunk's arrays, which then go the way parsed ones go
+            B.read_off.resize((size_t)n + 1); B.read_off[0] = 0;
+            for (int r = 0; r < n; ++r) B.read_off[(size_t)r + 1] = B.read_off[(size_t)r] + (int64_t)B.reads[(size_t)r].seq.size();
+            B.read_seq.resize((size_t)B.read_off[(size_t)n]);
+            const uint8_t *t4 = nt4_table();
+            parallel_blocks(n, threads, [&](int, int r0, int r1) {
+                for (int r = r0; r < r1; ++r) { const std::string &s = B.reads[(size_t)r].seq; uint8_t *d = B.read_seq.data() + B.read_off[(size_t)r]; for (size_t i = 0; i < s.size(); ++i) d[i] = t4[(unsigned char)s[i]]; }
+            });
+            static const uint8_t zero8 = 0;
+            lamsa_hp_seed_queries sq; memset(&sq, 0, sizeof sq);
+            sq.n_reads = n; sq.read_off = B.read_off.data(); sq.read_seq = B.read_seq.empty() ? &zero8 : B.read_seq.data();
+            sq.seed_len = P.seed_len; sq.seed_step = P.seed_step; sq.max_hits = P.per_aln_m;
+            sq.n_seqs = (int32_t)ix.off.size(); sq.seq_offset = ix.off.data(); sq.seq_len = ix.len.data();
+            lamsa_hp_batch sb; memset(&sb, 0, sizeof sb);
+            lamsa_hp_handle *hsd = seed_h[devs[(size_t)(n_seeded++ % (long)devs.size())]];
+            const double t1 = now_s();
+            int e;
+            { std::lock_guard<std::mutex> lk(fm_m); e = lamsa_hp_fm_seed(hsd, &sq, &sb); if (e == LAMSA_HP_OK) seed_kernel_ms += lamsa_hp_last_kernel_ms(hsd, 21) + lamsa_hp_last_kernel_ms(hsd, 22) + lamsa_hp_last_kernel_ms(hsd, 23); }
+            if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_seed failed: %d %s\n", e, lamsa_hp_last_error(hsd)); c->ret = 2; return c; }
+            const size_t ns = (size_t)sb.seed_off[n], nh = (size_t)sb.hit_off[ns];
+            B.seed_all.assign(sb.seed_all, sb.seed_all + n); B.last_len.assign(sb.last_len, sb.last_len + n); B.seed_off.assign(sb.seed_off, sb.seed_off + n + 1);
+            B.seed_id.assign(sb.seed_id, sb.seed_id + ns); B.hit_off.assign(sb.hit_off, sb.hit_off + ns + 1);
+            B.h_pos.assign(sb.h_pos, sb.h_pos + nh); B.h_chr.assign(sb.h_chr, sb.h_chr + nh); B.h_strand.assign(sb.h_strand, sb.h_strand + nh);
+            B.h_nm.assign(sb.h_nm, sb.h_nm + nh); B.h_len_dif.assign(sb.h_len_dif, sb.h_len_dif + nh); B.h_cig_n.assign(sb.h_cig_n, sb.h_cig_n + nh);
+            B.cig8.assign(sb.cig8, sb.cig8 + (size_t)sb.n_cig); B.cig_wide = false;
+            seed_s += now_s() - t1;
+            if (trace) fprintf(stderr, "[prepare] %d reads seeded in the FM index in %.3f s: %zu slots, %zu hits\n", n, now_s() - t1, ns, nh);
+            if (saver.fp && !saver.write(B)) { fprintf(stderr, "[lamsa_aln] writing %s failed\n", opt.save_hits.c_str()); c->ret = 1; }
+            parse_s += now_s() - t0;
+            return c;
         }
         const double t1 = now_s();
         // text -> hit records (gem_map_msg / map_cal_msg run inside the worker threads in the reference too)
@@ -1547,8 +1613,9 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
             fq.n_win = (int32_t)(all.win_off.size() - 1); fq.seq = all.seq.data(); fq.seq_bytes = (int64_t)all.seq.size(); fq.win_off = all.win_off.data();
             fq.k = P.bwt_seed_len; fq.max_occ = 500;                        // 5 * MAX_HIT (rescue.cpp): a seed with more rows is not located
             lamsa_hp_fm_out found; memset(&found, 0, sizeof found);
-            const int e = lamsa_hp_fm_search(h_dp, &fq, &found);
-            if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_search (stage 4) failed: %d %s\n", e, lamsa_hp_last_error(h_dp)); return 2; }
+            int e;
+            { std::unique_lock<std::mutex> lk(fm_m, std::defer_lock); if (seed_fm) lk.lock(); e = lamsa_hp_fm_search(h_fm, &fq, &found); }      // (the answers are the handle's until its next search: a seeding call leaves them alone)
+            if (e != LAMSA_HP_OK) { fprintf(stderr, "[lamsa_aln] lamsa_hp_fm_search (stage 4) failed: %d %s\n", e, lamsa_hp_last_error(h_fm)); return 2; }
             n_rescue_kmers += found.n_kmers;
             std::atomic<int> bad_found(0);
             parallel_blocks(n, threads, [&](int t, int r0, int r1) {
@@ -1684,6 +1751,8 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
         }
         if (scanned.valid()) scanned.wait();
         saver.close();
+        destroy_seed_handles();
+        if (seed_fm) fprintf(stderr, "[lamsa_aln] --seed-fm: %ld chunks seeded in %.2f s (kernels %.1f ms)\n", n_seeded, seed_s, seed_kernel_ms);
         if (stats) { stats->n_reads = n_reads; stats->n_bases = n_bases; stats->wall_s = now_s() - t_begin; stats->load_s = load_s; stats->parse_s = parse_s; }
         return ret;
     }
@@ -1716,6 +1785,8 @@ int run_aln(const Options &opt, const lamsa_hp_para &P, FILE *out, const std::st
     if (reserver.joinable()) reserver.join();
     for (lamsa_hp_handle *hh : hs) lamsa_hp_destroy(hh);
     if (h_dp) lamsa_hp_destroy(h_dp);
+    destroy_seed_handles();
+    if (seed_fm) fprintf(stderr, "[lamsa_aln] --seed-fm: %ld chunks seeded in %.2f s (kernels %.1f ms)\n", n_seeded, seed_s, seed_kernel_ms);
     if (trace) fprintf(stderr, "[write] %ld chunks written by all threads side by side (pwrite)\n", n_mapped_chunks);
     if (stats) { stats->n_reads = n_reads; stats->n_bases = n_bases; stats->n_bad = n_bad; stats->kernel_ms = kernel_ms;
                  stats->wall_s = now_s() - t_begin; stats->load_s = load_s; stats->parse_s = parse_s; stats->submit_s = submit_s; stats->wait_s = wait_s; stats->sam_s = sam_s; stats->reserve_s = reserve_s; }

@@ -109,6 +109,7 @@ struct Options {
     int tag_eqx = 0, tag_cs = 0;                          // --eqx: every printed CIGAR in =/X form (LAMSA_HP_TAG_EQX, include/lamsa_hp.h); --cs: cs:Z (short form) on every mapped record
     int paf = 0, paf_cg = 0;                              // --paf: PAF lines from the per-record summaries of the GPU (LAMSA_HP_TAG_SUMMARY); --paf-cg: PAF with cg:Z from the ordinary stream
     int rescue_gpu = 0;                                   // --rescue-gpu: the exact search of stage 4 on the GPU, one lamsa_hp_fm_search per chunk (include/lamsa_hp.h)
+    int seed_fm = 0;                                      // --seed-fm: the seeds of every chunk searched exactly in the FM index on the GPU, one lamsa_hp_fm_seed per chunk: no GEM mapper, no map text
     int left_align = 0;                                   // --left-align: the gaps of every printed CIGAR shifted as far left as they go (LAMSA_HP_TAG_LEFT_ALIGN, include/lamsa_hp.h)
     float ed_rate = -1, mis_rate = -1, mat_rate = -1;     // -e, -x; defaults per read type (src/lamsa_aln.h:26-70)
     std::string gem_dir;                                  // directory holding gem-mapper (default: <directory of this binary>/gem)

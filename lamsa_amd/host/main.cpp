@@ -4,7 +4,7 @@
 // Seeding works as in the reference: unless -N (or --seed-result FILE) is given, the reads are cut into seeds and the
 // GEM mapper of the reference's bundle is run on them (--gem-dir DIR, default <directory of this binary>/gem; the
 // <ref>.gem index comes from `lamsa index`, here or the reference's).  Stage (4), the BWT rescue, needs <ref>.bwt and
-// <ref>.sa and is skipped with a note when they are missing.  `lamsa index` (index.cpp) writes the reference's index files.
+// <ref>.sa and is skipped with a note when they are missing.  --seed-fm seeds on the GPU instead, exactly, in that FM index (no mapper).  `lamsa index` (index.cpp) writes the reference's index files.
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +43,11 @@ static int usage()
                     "         --paf-cg (the same lines with cg:Z, the record's CIGAR without its clips, from the ordinary result stream: honours --eqx, --left-align,\n"
                     "         --MD and --cs as SAM does; not with --SA or --paf),\n"
                     "         --rescue-gpu (stage 4: the exact search of the -k mers of all uncovered regions of a chunk in one call on the GPU, in an FM index\n"
-                    "         kept in its memory, instead of one query at a time on the host threads; same output; nothing to do with -R 0)\n\n");
+                    "         kept in its memory, instead of one query at a time on the host threads; same output; nothing to do with -R 0),\n"
+                    "         --seed-fm (seed on the GPU instead of with the GEM mapper: the -l mers of every chunk, -i apart, are searched exactly in the FM index\n"
+                    "         <ref>.bwt / <ref>.sa kept in GPU memory, a seed with more than -p occurrences is dropped; no gem-mapper, no <ref>.gem, no seed or map files.\n"
+                    "         Exact seeds suit accurate reads (about 1 %% error); noisy reads keep GEM or take shorter seeds (-l, -i).  Not with -N, --seed-result, --hits,\n"
+                    "         --seed-first or -l above 63; the output differs from a GEM run, which also lists inexact hits)\n\n");
     return 1;
 }
 
@@ -74,7 +78,7 @@ int main(int argc, char *argv[])
         {"max-skel",1,0,'s'},{"max-reg",1,0,'R'},{"bwt-kmer",1,0,'k'},{"fastest",0,0,'f'},{"ed-rate",1,0,'e'},{"diff-rate",1,0,'d'},
         {"mis-rate",1,0,'x'},{"read-type",1,0,'T'},{"match-sc",1,0,'m'},{"mis-pen",1,0,'M'},{"open-pen",1,0,'O'},{"ext-pen",1,0,'E'},
         {"band-width",1,0,'w'},{"end-bonus",1,0,'b'},{"max-out",1,0,'r'},{"gap-split",1,0,'g'},{"soft-clip",0,0,'S'},{"comment",0,0,'C'},
-        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{"left-align",0,0,1014},{"paf",0,0,1015},{"paf-cg",0,0,1016},{"rescue-gpu",0,0,1017},{0,0,0,0}};
+        {"output",1,0,'o'},{"help",0,0,'h'},{"HELP",0,0,'H'},{"device",1,0,1000},{"gem-dir",1,0,1003},{"seed-result",1,0,1001},{"batch",1,0,1002},{"parse-only",0,0,1004},{"save-hits",1,0,1005},{"hits",1,0,1006},{"devices",1,0,1007},{"seed-first",0,0,1008},{"shard",1,0,1009},{"MD",0,0,1010},{"SA",0,0,1011},{"eqx",0,0,1012},{"cs",0,0,1013},{"left-align",0,0,1014},{"paf",0,0,1015},{"paf-cg",0,0,1016},{"rescue-gpu",0,0,1017},{"seed-fm",0,0,1018},{0,0,0,0}};
     optind = 2;
     while ((c = getopt_long(argc, argv, "t:l:i:p:V:v:s:R:k:fm:M:O:E:w:b:e:d:x:T:r:g:SCo:hHNI", lopt, NULL)) >= 0) {
         switch (c) {
@@ -130,6 +134,7 @@ int main(int argc, char *argv[])
             case 1015: opt.paf = 1; break;
             case 1016: opt.paf_cg = 1; break;
             case 1017: opt.rescue_gpu = 1; break;
+            case 1018: opt.seed_fm = 1; break;
             case 1007: { opt.devices.clear(); for (const char *q = optarg; *q;) { opt.devices.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q == ',') ++q; } break; }
         case 1001: opt.seed_result = optarg; break;
         case 1002: opt.chunk_reads = atoi(optarg) > 0 ? atoi(optarg) : opt.chunk_reads; break;
@@ -142,13 +147,19 @@ int main(int argc, char *argv[])
     if (opt.paf && opt.paf_cg) { fprintf(stderr, "[lamsa_aln] --paf and --paf-cg exclude each other\n"); return 1; }
     if ((opt.paf || opt.paf_cg) && opt.tag_sa) { fprintf(stderr, "[lamsa_aln] --SA is a SAM tag: not with --paf / --paf-cg\n"); return 1; }
     if (opt.paf && (opt.tag_md || opt.tag_cs || opt.tag_eqx)) { fprintf(stderr, "[lamsa_aln] --MD, --cs and --eqx need the CIGARs, which --paf does not fetch: use --paf-cg\n"); return 1; }
+    // --seed-fm is a seed source of its own: what names another one, or shapes seeds the device does not cut, is refused before any work
+    if (opt.seed_fm) {
+        const char *why = opt.no_seed_aln && opt.hits.empty() ? "-N reuses a GEM map" : !opt.seed_result.empty() ? "--seed-result names a GEM map" : !opt.hits.empty() ? "--hits reads a stored hit stream" :
+                          opt.seed_first ? "--seed-first is about the GEM mapper" : P.seed_len > 63 ? "-l above 63 (a seed's CIGAR element is kept in 6 bits)" : nullptr;
+        if (why) { fprintf(stderr, "[lamsa_aln] --seed-fm seeds the reads in the FM index on the GPU: not with %s\n", why); return 2; }
+    }
     opt.ref_prefix = argv[optind]; opt.reads = argv[optind + 1];
     if (opt.gem_dir.empty()) {                                       // get_bin_dir, src/lamsa_aln.c: <directory of the executable>/gem
         std::string self = argv[0];
         const size_t sl = self.rfind('/');
         opt.gem_dir = (sl == std::string::npos ? std::string(".") : self.substr(0, sl)) + "/gem";
     }
-    if (!opt.no_seed_aln && opt.seed_result.empty()) {
+    if (!opt.no_seed_aln && opt.seed_result.empty() && !opt.seed_fm) {
         // the mapper is started here, before any GPU call of this process, and (unless --seed-first) left running: run_aln reads its map as it grows
         const int src = lamsa::run_seeding(opt, P, opt.seed_first || opt.parse_only ? nullptr : &opt.mapper_pid);
         if (src) return src;

@@ -71,6 +71,36 @@ class HpFmOut(C.Structure):
                 ("pos_off", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_uint64))]
 
 
+class HpSeedQueries(C.Structure):
+    """struct lamsa_hp_seed_queries"""
+    _fields_ = [("n_reads", C.c_int32), ("read_off", C.c_void_p), ("read_seq", C.c_void_p), ("seed_len", C.c_int32), ("seed_step", C.c_int32), ("max_hits", C.c_int32),
+                ("n_seqs", C.c_int32), ("seq_offset", C.c_void_p), ("seq_len", C.c_void_p)]
+
+
+def seed_batch_arrays(b):
+    """The arrays of the lamsa_hp_batch a lamsa_hp_fm_seed filled in (compact form), copied: a dict by field name; h_cig_off and cig
+    are None as in the struct, read_seq is left to the caller (it is the caller's array)."""
+    n = int(b.n_reads)
+
+    def arr(p, ct, k):
+        if not p:
+            raise RuntimeError("lamsa_hp_fm_seed handed out a null pointer")
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (max(k, 1),))[:k].copy()
+    d = dict(n_reads=n, n_cig=int(b.n_cig), h_cig_off=None if not b.h_cig_off else b.h_cig_off, cig=None if not b.cig else b.cig)
+    if not b.read_seq:
+        raise RuntimeError("lamsa_hp_fm_seed handed out a null pointer")
+    d["read_off"] = arr(b.read_off, C.c_int64, n + 1) if n else np.zeros(1, np.int64)
+    d["seed_all"] = arr(b.seed_all, C.c_int32, n); d["last_len"] = arr(b.last_len, C.c_int32, n)
+    d["seed_off"] = arr(b.seed_off, C.c_int64, n + 1)
+    ns = int(d["seed_off"][n])
+    d["seed_id"] = arr(b.seed_id, C.c_int32, ns); d["hit_off"] = arr(b.hit_off, C.c_int64, ns + 1)
+    nh = int(d["hit_off"][ns])
+    d["h_pos"] = arr(b.h_pos, C.c_int64, nh); d["h_chr"] = arr(b.h_chr, C.c_int32, nh); d["h_strand"] = arr(b.h_strand, C.c_int8, nh)
+    d["h_nm"] = arr(b.h_nm, C.c_int16, nh); d["h_len_dif"] = arr(b.h_len_dif, C.c_int16, nh); d["h_cig_n"] = arr(b.h_cig_n, C.c_uint8, nh)
+    d["cig8"] = arr(b.cig8, C.c_uint8, int(b.n_cig))
+    return d
+
+
 def read_fm_index(prefix):
     """<prefix>.bwt / <prefix>.sa (the reference's index files) as the arrays of lamsa_hp_fm_index: (struct, arrays kept alive)."""
     hdr = np.fromfile(prefix + ".bwt", np.uint64, 5)
@@ -104,7 +134,7 @@ EXPORTS = ("lamsa_hp_para_init", "lamsa_hp_para_finish", "lamsa_hp_create", "lam
            "lamsa_hp_align_batch", "lamsa_hp_upload_batch", "lamsa_hp_run_uploaded",
            "lamsa_hp_submit_batch", "lamsa_hp_collect_batch", "lamsa_hp_host_alloc", "lamsa_hp_host_free",
            "lamsa_hp_start_uploaded", "lamsa_hp_finish_uploaded", "lamsa_hp_reserve", "lamsa_hp_set_result_tags",
-           "lamsa_hp_fm_load", "lamsa_hp_fm_search")
+           "lamsa_hp_fm_load", "lamsa_hp_fm_search", "lamsa_hp_fm_seed")
 
 TAG_MISMATCHES = 1      # LAMSA_HP_TAG_MISMATCHES: every record of the result stream also lists its mismatches
 TAG_EQX = 2             # LAMSA_HP_TAG_EQX: the CIGARs of the result stream are in =/X form (every M split into '=' 7 and 'X' 8 pieces)
@@ -172,6 +202,8 @@ def load_library(path=None):
         L.lamsa_hp_fm_load.restype = C.c_int
         L.lamsa_hp_fm_search.argtypes = [C.c_void_p, C.POINTER(HpFmQueries), C.POINTER(HpFmOut)]
         L.lamsa_hp_fm_search.restype = C.c_int
+        L.lamsa_hp_fm_seed.argtypes = [C.c_void_p, C.POINTER(HpSeedQueries), C.POINTER(HpBatch)]
+        L.lamsa_hp_fm_seed.restype = C.c_int
         _lib = L
     return _lib
 
@@ -298,6 +330,24 @@ class LamsaHp:
         if rc != 0:
             raise RuntimeError("lamsa_hp_fm_search: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
         return fm_result(O, n_win)
+
+    def fm_seed(self, read_off, read_seq, seed_len, seed_step, max_hits, seq_offset, seq_len):
+        """Seed the reads read_seq[read_off[r] : read_off[r + 1]] (base codes 0..4) in the loaded index: every seed_step-th window of
+        seed_len bases searched exactly, its located rows turned into hit records as include/lamsa_hp.h defines (strand, contig, bounds;
+        a seed with more than max_hits rows keeps an empty slot).  seq_offset / seq_len: the contig table of the index's reference.
+        Returns the arrays of the lamsa_hp_batch as numpy copies, a dict by field name (compact form: h_cig_off and cig are None);
+        with n_reads and read_seq it is a batch align_batch / submit_batch take."""
+        read_off = np.ascontiguousarray(read_off, np.int64); read_seq = np.ascontiguousarray(read_seq, np.uint8)
+        seq_offset = np.ascontiguousarray(seq_offset, np.int64); seq_len = np.ascontiguousarray(seq_len, np.int32)
+        Q = HpSeedQueries(max(len(read_off) - 1, 0), read_off.ctypes.data, read_seq.ctypes.data, int(seed_len), int(seed_step), int(max_hits),
+                          len(seq_len), seq_offset.ctypes.data, seq_len.ctypes.data)
+        b = HpBatch()
+        rc = self.L.lamsa_hp_fm_seed(self._h, C.byref(Q), C.byref(b))
+        if rc != 0:
+            raise RuntimeError("lamsa_hp_fm_seed: %d %s" % (rc, self.L.lamsa_hp_last_error(self._h).decode()))
+        d = seed_batch_arrays(b)
+        d["read_seq"] = read_seq
+        return d
 
     # ---- the hot path proper
     def _batch_struct(self, batch):
